@@ -10,7 +10,15 @@ region; nothing leaves HBM inside it.  Consecutive steps cycle through independe
 the 256 MB Infinity Cache between steps: the rate is the HBM rate.  One process per GPU (torchrun), ranks shard the images
 (no data-path collective: images are independent), max-over-ranks timing.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, autotunes, warms up, times the K steps and prints the line.  The autotune
+(autotune_rotating, ~2 s on config 2) stays in a plain run because it chooses the kernel instance
+the steps time: `value` without it would be another kernel's rate.  --full also runs,
+after the timed steps, what is not the headline figure: the CPU baseline and the drop-in class's
+per-call cost, the bit-exact check of the built pyramids against the reference's checksums
+(`parity`) and the query of the GPU's clocks.  --dump-outputs DIR writes what the last timed step
+built (dump_outputs); with the same arguments the inputs are the same in every run.
 
 --gpus N > 1 without a launcher (WORLD_SIZE unset) starts N rank processes itself — one per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 and a file rendezvous (GDP_BENCH_RDV) in
@@ -822,6 +830,42 @@ def verify(ctx, cfg, key, world, rank, dist, mg, first_image, subset=False):
                         "oracle closed form (non-square input: no reference output exists)")}
 
 
+DUMP_IMAGES = 4         # --dump-outputs: images of a rank's last-step batch that are written
+DUMP_VALUES = 12 << 20  # ... and float32 values in ALL files of a run, every rank's together (48 MiB < 64 MB)
+
+
+def dump_positions(n, k):
+    """k distinct, sorted positions in [0, n) (n > k), the same in every run: one drawn from SEED
+    in each of the k strides [i * n // k, (i + 1) * n // k), so they span the whole array without
+    duplicates."""
+    import numpy as np
+
+    edges = np.arange(k + 1, dtype=np.int64) * n // k
+    return edges[:-1] + np.random.default_rng(SEED).integers(0, edges[1:] - edges[:-1])
+
+
+def dump_outputs(out_dir, ctx, batch, rank, world):
+    """--dump-outputs: what the last timed step left in its buffer set, as a caller would download
+    it (PyramidContext.pyramid: the packed [octave][scale][row][col] float32 pyramid), for up to
+    DUMP_IMAGES images spread evenly over the rank's batch.  The run's DUMP_VALUES values are shared
+    equally among every rank's files; a pyramid of more values than its file's share is written as
+    its values at that many positions (dump_positions: the same for every image, run and build),
+    so two builds given the same arguments write comparable files:
+    DIR/pyramid[_rank<r>]_image<b>.npy."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    ctx.sync()
+    picks = sorted({(batch - 1) * i // max(1, DUMP_IMAGES - 1) for i in range(DUMP_IMAGES)}) if batch > 1 else [0]
+    n = ctx.packed_floats()
+    share = max(1, DUMP_VALUES // (world * len(picks)))
+    at = dump_positions(n, share) if n > share else None
+    tag = "" if world == 1 else f"_rank{rank}"
+    for b in picks:
+        pyr = ctx.pyramid(b)
+        np.save(os.path.join(out_dir, f"pyramid{tag}_image{b}.npy"), pyr if at is None else pyr[at])
+
+
 INPLACE_CALLS = {"regen": 3, "gauss": 2}  # checksums_inplace.json's K per op
 
 
@@ -945,9 +989,23 @@ def main():
     ap.add_argument("--rotate", type=int, default=None,
                     help="independent input+pyramid buffer sets the steps cycle through (default: enough to "
                          "exceed %d MiB, so no step finds its lines in the 256 MB Infinity Cache)" % (ROTATE_BYTES >> 20))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is not the headline figure: the CPU "
+                         "baseline and the drop-in class's per-call cost (--no-cpu skips both), the bit-exact "
+                         "check of what the steps built against the reference's checksums (`parity`), and the "
+                         "rocm-smi query of the GPU's clocks.  A plain run sets up, autotunes (the search picks "
+                         "the kernel instance that `value` times, so it stays; --no-autotune / --variant skip "
+                         "it), warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                         "(float32): the packed pyramid of up to %d images per rank of that step's buffer set, "
+                         "whole when small, else its values at fixed seeded positions; %d values in all files "
+                         "of the run together" % (DUMP_IMAGES, DUMP_VALUES))
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if not args.full:  # a plain run: the headline figure only (nothing but --full samples the CPU)
+        args.no_cpu = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: start the N ranks here, before torch is imported or a GPU is touched
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -1133,7 +1191,10 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     kernel_ms = ev0.elapsed_time(ev1) / args.steps  # per-launch, HIP events on the launch stream
-    topology["gpu_state_after_timed_steps"] = gpu_state(topology["devices"][0]["pci"]) if rank == 0 else None
+    if args.dump_outputs:  # before anything else launches on the buffer sets
+        dump_outputs(args.dump_outputs, ctxs[(n_step[0] - 1) % rotate], 1 if cfg["band"] else B, rank, world)
+    topology["gpu_state_after_timed_steps"] = (gpu_state(topology["devices"][0]["pci"])
+                                               if rank == 0 and args.full else None)
     if dist:  # every rank's own timing, recorded beside the max that the line reports
         per_rank = [None] * world
         dist.all_gather_object(per_rank, {"rank": rank, "ms_per_step": round(wall * 1e3 / args.steps, 6),
@@ -1141,10 +1202,10 @@ def main():
         topology["per_rank"] = per_rank
     wall, kernel_ms = mg.max_over_ranks([wall, kernel_ms], dist=dist, device=red_dev)
     parity = (verify(ctx, cfg, args.config, world, rank, dist, mg, first_image, subset=args.op == "subset")
-              if args.op in ("build", "subset") else None)
-    if halo_exchange:
+              if args.full and args.op in ("build", "subset") else None)
+    if args.full and halo_exchange:
         parity = verify_conv_bands(ctx, cfg, world, rank, dist, mg, args.input)
-    if args.op in ("regen", "gauss") and not cfg["band"]:
+    if args.full and args.op in ("regen", "gauss") and not cfg["band"]:
         parity = verify_inplace(ctx, cfg, args.op, stream, world, rank, dist, mg, first_image)
     if parity is not None and rotate > 1 and args.op not in ("regen", "gauss"):
         # every rotated set built the same images: their checksums must all equal set 0's
@@ -1255,7 +1316,9 @@ def main():
     }
     result["parity"] = parity if (args.op in ("build", "subset", "regen", "gauss") or halo_exchange) else (
         {"status": "extension: no reference output (tests/ check it against a float64 convolution)"})
-    if result["parity"] is None:  # an in-place op on the row-band config
+    if not args.full:
+        result["parity"] = {"status": "unchecked (a plain run only times the steps; --full checks them)"}
+    elif result["parity"] is None:  # an in-place op on the row-band config
         result["parity"] = {"status": "unchecked (no reference re-entry fixture of this workload)"}
     if autotuned:  # outside the timed region: the search that picked the kernel instance
         result["autotune"] = {"seconds": round(tune_s, 2), "candidates": (

@@ -354,3 +354,108 @@ def test_serving_figure_is_opt_in():
     assert re.search(r'"--concurrent-streams", type=int, default=0', src)
     main = src[src.index("def main():"):]
     assert main.index("concurrent_streams(ctxs") < main.index("for _ in range(args.warmup):")
+
+
+class _FakeContext:
+    """What bench.dump_outputs uses of a PyramidContext: image b's packed pyramid is b + position % 4096."""
+
+    def __init__(self, n):
+        import numpy as np
+
+        self.n = n
+        self.base = (np.arange(n, dtype=np.int64) % 4096).astype(np.float32)
+
+    def sync(self):
+        pass
+
+    def packed_floats(self):
+        return self.n
+
+    def pyramid(self, b=0):
+        return self.base + b
+
+
+def test_dump_positions_are_distinct_sorted_and_span_the_array():
+    import numpy as np
+
+    n, k = 111_738_880, 12 << 20  # config 2's packed pyramid, a one-image run's share
+    at = bench.dump_positions(n, k)
+    assert at.shape == (k,) and at[0] >= 0 and at[-1] < n
+    assert np.all(np.diff(at) > 0)  # sorted, no position twice
+    assert at[0] <= n // k and at[-1] >= n - n // k - 2  # the first and the last stride are both sampled
+    assert np.diff(at).max() <= 2 * (n // k + 1)  # and every stride between them
+    assert np.array_equal(at, bench.dump_positions(n, k))  # the same in every run
+
+
+def test_dump_outputs_small_pyramids_are_written_whole(tmp_path):
+    import numpy as np
+
+    bench.dump_outputs(str(tmp_path), _FakeContext(1000), 1, 0, 1)
+    assert sorted(os.listdir(tmp_path)) == ["pyramid_image0.npy"]
+    got = np.load(tmp_path / "pyramid_image0.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, _FakeContext(1000).pyramid(0))
+
+
+@pytest.mark.parametrize("world,batch,images", [(1, 1, [0]), (3, 64, [0, 21, 42, 63]), (8, 2, [0, 1])])
+def test_dump_outputs_of_every_rank_together_stay_within_64_mb(tmp_path, world, batch, images):
+    """--dump-outputs: every rank writes into the same DIR, and ALL files of the run together hold
+    at most 64 MB, at any world size — float32 values of up to DUMP_IMAGES images per rank (first
+    and last of the batch among them) at the same positions in every image and every run."""
+    import numpy as np
+
+    ctx = _FakeContext(bench.DUMP_VALUES + 12345)  # larger than any file's share
+    for d in ("a", "b"):  # two runs with the same arguments
+        for rank in range(world):
+            bench.dump_outputs(str(tmp_path / d), ctx, batch, rank, world)
+    tag = (lambda r: "") if world == 1 else (lambda r: f"_rank{r}")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(f"pyramid{tag(r)}_image{b}.npy" for r in range(world) for b in images)
+    assert len(images) <= bench.DUMP_IMAGES
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in names)
+    assert total <= 64_000_000, total
+    share = bench.DUMP_VALUES // (world * len(images))
+    at = bench.dump_positions(ctx.n, share)
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float32 and a.shape == (share,) and np.array_equal(a, b)
+        assert np.array_equal(a, ctx.pyramid(int(name.split("image")[1][:-4]))[at]), name
+
+
+@pytest.mark.gpu
+def test_plain_run_times_only_and_dumps_what_its_last_step_built(tmp_path):
+    """A plain bench.py run (no --full) carries no CPU baseline, no drop-in cost, no parity check and
+    no rocm-smi query, and --dump-outputs writes what its timed path built: here two 1080x1920
+    images per step (config 3 with --batch 2), each file the values of that image's pyramid — built
+    in this test by a context of its own from the same synthetic input — at dump_positions."""
+    import json
+    import subprocess
+
+    import numpy as np
+
+    import __graft_entry__ as entry
+
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--config", "c3", "--batch", "2",
+                        "--rotate", "2", "--steps", "3", "--warmup", "1", "--no-autotune", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["cpu_baseline"] is None and "dropin_call" not in line
+    assert line["parity"]["status"].startswith("unchecked (a plain run")
+    assert line["topology"]["gpu_state_after_timed_steps"] is None
+    assert sorted(os.listdir(out)) == ["pyramid_image0.npy", "pyramid_image1.npy"]
+    pkg = entry.load_package()
+    cfg = bench.CONFIGS["c3"]
+    with pkg.PyramidContext(cfg["H"], cfg["W"], S=2, octaves=cfg["O"], batch=2) as ctx:
+        ctx.fill_synthetic(bench.SEED, 0)
+        ctx.build()
+        ctx.sync()
+        share = bench.DUMP_VALUES // 2
+        assert ctx.packed_floats() > share
+        at = bench.dump_positions(ctx.packed_floats(), share)
+        for b in (0, 1):
+            got = np.load(out / f"pyramid_image{b}.npy")
+            assert got.dtype == np.float32
+            assert np.array_equal(got.view(np.uint32), ctx.pyramid(b)[at].view(np.uint32)), b
+    assert not np.array_equal(np.load(out / "pyramid_image0.npy"), np.load(out / "pyramid_image1.npy"))

@@ -1423,8 +1423,9 @@ def test_bench_selflaunched_ranks_certify_their_work(tmp_path):
                       (["--op", "conv", "--config", "c5", "--steps", "2", "--warmup", "1"], "conv")):
         logs = tmp_path / key
         env = dict(os.environ, GDP_BENCH_BACKEND="gloo", GDP_BENCH_RANK_LOGS=str(logs))
-        r = subprocess.run(["python3", os.path.join(REPO, "bench.py"), "--gpus", "2"] + args, env=env, timeout=240,
-                           capture_output=True, text=True)
+        # --full: the line's `parity` (and, for the conv run, the CPU baseline) are not part of a plain run
+        r = subprocess.run(["python3", os.path.join(REPO, "bench.py"), "--gpus", "2", "--full"] + args, env=env,
+                           timeout=240, capture_output=True, text=True)
         assert r.returncode == 0, (key, f"rank stderr kept in {logs}", _rank_failure(r.stderr))
         line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
         assert line["n_gpus"] == 2, key
@@ -1449,7 +1450,7 @@ def test_bench_band_scatter_and_gather_collector():
 
     env = dict(os.environ, GDP_BENCH_BACKEND="gloo")
     r = subprocess.run(["python3", os.path.join(REPO, "bench.py"), "--gpus", "2", "--config", "c5", "--steps", "2",
-                        "--warmup", "1", "--no-cpu", "--no-autotune", "--scatter", "--gather"],
+                        "--warmup", "1", "--full", "--no-cpu", "--no-autotune", "--scatter", "--gather"],
                        env=env, timeout=280, capture_output=True, text=True)
     assert r.returncode == 0, _rank_failure(r.stderr)
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -2,12 +2,14 @@
 """PMC record of the kernel a bench.py line timed (any --op), from two separate rocprofv3 --pmc
 passes of the SAME bench.py command (FETCH_SIZE, then WRITE_SIZE):
 
-    rocprofv3 --pmc FETCH_SIZE -d gpurun_out/p_fetch -o run --output-format csv -- python3 bench.py <args> --no-cpu
-    rocprofv3 --pmc WRITE_SIZE -d gpurun_out/p_write -o run --output-format csv -- python3 bench.py <args> --no-cpu
-    python3 tools/pmc_bench.py --fetch gpurun_out/p_fetch --write gpurun_out/p_write \\
-        --bench-log gpurun_out/<the FETCH pass's stdout> --kernel k_conv_blk --round r05 --tag c2_conv_h8
+    rocprofv3 --pmc FETCH_SIZE -d OUT/p_fetch -o run --output-format csv -- python3 bench.py <args> --full --no-cpu
+    rocprofv3 --pmc WRITE_SIZE -d OUT/p_write -o run --output-format csv -- python3 bench.py <args> --full --no-cpu
+    python3 tools/pmc_bench.py --fetch OUT/p_fetch --write OUT/p_write \\
+        --bench-log OUT/<the FETCH pass's stdout> --kernel k_conv_blk --round r05 --tag c2_conv_h8
 
-Reads = 2 x FETCH_SIZE KiB (the guide's gfx950 correction, calibrated for this kernel's access
+(OUT: any scratch directory.  --full: the stored line, `bench_line_of_traced_run`, carries the parity
+check of the traced run, which a plain bench.py run leaves out; tests/test_bench_accounting.py asserts
+it for the in-place records.)  Reads = 2 x FETCH_SIZE KiB (the guide's gfx950 correction, calibrated for this kernel's access
 widths in round 4: profiles/calib_fetch_r04a.json), writes = WRITE_SIZE KiB; the median over the
 dispatches of the named kernel (the bench's warm-up, autotune and timed launches alike: every
 candidate moves the same bytes).  Writes profiles/pmc_<tag>_<round>.json with the bench line's

@@ -10,7 +10,7 @@ for op in regen gauss; do
   subs="${REGEN_SUBS:-1 4 2 0 8 16}"; [ $op = gauss ] && subs="${GAUSS_SUBS:-1 4 2 8 16}"
   for sub in $subs; do
     tag="${cfg}_${op}_s${sub}${zt}_${rnd}"
-    force="--op ${op} --inplace-sub ${sub} --zero-window ${zw} --no-cpu"
+    force="--op ${op} --inplace-sub ${sub} --zero-window ${zw} --full --no-cpu"  # --full: the line's parity goes into the record
     steps+=("prof_${tag}_trace|300|rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${tag}_trace -o run --output-format csv -- python3 bench.py --config ${cfg} --steps 50 --warmup 5 ${force} > gpurun_out/prof_${tag}_trace.json")
     steps+=("prof_${tag}_fetch|180|timeout -s KILL 170 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/prof_${tag}_fetch -o run --output-format csv -- python3 bench.py --config ${cfg} --steps 5 --warmup 1 ${force}")
     steps+=("prof_${tag}_write|180|timeout -s KILL 170 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/prof_${tag}_write -o run --output-format csv -- python3 bench.py --config ${cfg} --steps 5 --warmup 1 ${force}")
