@@ -59,6 +59,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
+#include <vector>
 
 #include "gdp.h"
 
@@ -83,6 +84,13 @@ public:
     // it may be called any number of times; each call continues from the current contents.
     void GenerateDoG_mpi(int argc, char** argv);
     void GenerateDoG_mgpu(int argc, char** argv) { GenerateDoG_mpi(argc, argv); }  // SURVEY §8(f2) name
+    // Extension (no reference counterpart): the strict scale-space extrema of the current pyramid
+    // (levels 0..S+1 as DoG levels), found on the device and returned sorted by (octave, scale, row,
+    // col) — gdp_detect_extrema in gdp.h has the exact rules.  Pending host edits of GaussPy are
+    // uploaded first, as before every mutating call; the pyramid itself is not changed, so GaussPy
+    // is neither published nor downloaded again.  At most the context's keypoint capacity (65536
+    // unless gdp_set_keypoint_capacity(context(), n) raised it) records come back.
+    std::vector<gdp_keypoint> DetectExtrema(float contrast_threshold = 0.f, float edge_ratio = 0.f);
     ~GaussPyramid_hip();
     bool initialized;
     bool mirror_host;  // GaussPy two-way: upload before / download after every mutating call (default true)
@@ -360,6 +368,20 @@ inline void GaussPyramid_hip::GenerateDoG_mpi(int, char**) {
     fresh_ = false;
     check_(ctx_, gdp_sync(ctx_), "GenerateDoG_mpi");
     if (mirror_host) publish_();
+}
+
+inline std::vector<gdp_keypoint> GaussPyramid_hip::DetectExtrema(float contrast_threshold, float edge_ratio) {
+    CallScope scope(this);
+    const bool clean = armed_;
+    pull_host_();
+    armed_ = clean;  // the detection leaves the device pyramid alone: the record of written pages stays valid
+    check_(ctx_, gdp_detect_extrema(ctx_, contrast_threshold, edge_ratio, nullptr), "DetectExtrema");
+    size_t found = 0, stored = 0;
+    check_(ctx_, gdp_keypoint_count(ctx_, 0, &found), "DetectExtrema");
+    std::vector<gdp_keypoint> out(found);
+    check_(ctx_, gdp_download_keypoints(ctx_, 0, out.data(), out.size(), &stored, nullptr), "DetectExtrema");
+    out.resize(stored);
+    return out;
 }
 
 inline void GaussPyramid_hip::output() {  // :89-104

@@ -188,6 +188,64 @@ int gdp_input_halo(gdp_ctx* ctx, int side /* 0 above, 1 below */, void** rows, s
 int gdp_bind_input_halo(gdp_ctx* ctx, const void* above, const void* below, size_t pitch, size_t image_stride);
 int gdp_device_input(const gdp_ctx* ctx, int b, const void** rows, size_t* pitch);
 
+/* ---- extension: scale-space extrema (keypoints) on the device ---------------------------------
+ * The next SIFT step done where the pyramid already is (no reference counterpart, no parity claim):
+ * the local extrema of the DoG levels in space and scale, as a compact list of 16-byte records —
+ * a caller needs no host copy of the pyramid to find them.  It runs on whatever the pyramid
+ * CURRENTLY holds (the context's own buffer or one bound with gdp_set_output_device): most
+ * meaningful after gdp_build_gaussian, whose DoG is a real scale space, but the reference's window
+ * pyramid works too.  Out of scope: sub-pixel refinement, orientation assignment, descriptors.
+ *
+ * For image b and octave o (rows x cols as held by the context), levels 0..S+1 are taken as the
+ * DoG levels D; level S+2 is never read.  Candidates are s in [1, S], r in [1, rows-2],
+ * c in [1, cols-2]; octaves under 3 x 3 and contexts with S = 0 yield nothing (the calls succeed,
+ * count 0).  A candidate v = D[s][r][c] is a keypoint when
+ *   1. it is a STRICT extremum: v > n for all 26 neighbours n in {s-1,s,s+1} x {r-1,r,r+1} x
+ *      {c-1,c,c+1} (kind +1), or v < n for all 26 (kind -1).  Plain IEEE float32 comparisons,
+ *      denormals kept: ties are not extrema (the window pyramid's +0 plateaus give nothing),
+ *      -0 == +0, and a NaN among the 27 values disqualifies the candidate;
+ *   2. fabsf(v) > contrast_threshold;
+ *   3. when edge_ratio != 0, with every operation a separately rounded float32 operation (no
+ *      contraction) in exactly this order
+ *        dxx = (D[s][r][c+1] + D[s][r][c-1]) - 2.0f*v
+ *        dyy = (D[s][r+1][c] + D[s][r-1][c]) - 2.0f*v
+ *        dxy = ((D[s][r+1][c+1] - D[s][r+1][c-1]) - (D[s][r-1][c+1] - D[s][r-1][c-1])) * 0.25f
+ *        tr  = dxx + dyy,  det = dxx*dyy - dxy*dxy
+ *      det > 0.0f && (tr*tr)*edge_ratio < ((edge_ratio+1.0f)*(edge_ratio+1.0f))*det.
+ * The result is an exact set.  contrast_threshold must be >= 0 (not NaN), edge_ratio 0 or finite
+ * and >= 1 (GDP_ERR_ARG otherwise).  Row-band contexts are refused with GDP_ERR_STATE (the
+ * neighbourhood crosses band edges); whole-image contexts of any batch size are supported;
+ * contexts with S x (pixels of one image's octaves) >= 2^32 are refused with GDP_ERR_ARG (the
+ * counter is 32-bit). */
+typedef struct gdp_keypoint {   /* 16 bytes, one 16-B store per record */
+    uint16_t octave; uint8_t scale; int8_t kind;   /* +1 maximum, -1 minimum */
+    int32_t row, col;                               /* in level (octave, scale) */
+    float value;                                    /* D[scale][row][col] */
+} gdp_keypoint;
+/* Records the context keeps per image (default 65536).  The context owns a [batch][capacity]
+ * record buffer and [batch] uint32 counters, allocated on first use; setting another capacity
+ * reallocates the buffer (after draining the device; earlier results are dropped).  0 is
+ * GDP_ERR_ARG. */
+int gdp_set_keypoint_capacity(gdp_ctx* ctx, size_t per_image);
+/* Detect on every image of the batch: zeroes the counters on `stream`, then ONE launch over all
+ * images and octaves (asynchronous and stream-ordered, like gdp_build).  More keypoints may be
+ * found than the capacity holds: the counter still counts them all, the buffer then holds exactly
+ * `capacity` distinct true keypoints (which ones is unspecified) and nothing is stored at or
+ * beyond `capacity`.  The device order of the records is unspecified. */
+int gdp_detect_extrema(gdp_ctx* ctx, float contrast_threshold, float edge_ratio, void* stream);
+/* Keypoints the last detection found in image b (blocking; waits for the context's OWN stream,
+ * like the blocking copies below; 0 before any detection). */
+int gdp_keypoint_count(gdp_ctx* ctx, int b, size_t* found);
+/* Copy min(found, the context's capacity, `capacity`) records of image b to `host` (blocking),
+ * sorted ascending by (octave, scale, row, col), so host results are the same run to run.
+ * *stored = records written, *found = gdp_keypoint_count (either may be NULL). */
+int gdp_download_keypoints(gdp_ctx* ctx, int b, gdp_keypoint* host, size_t capacity,
+                           size_t* stored, size_t* found);
+/* Zero-copy view for device consumers: image b's record buffer (capacity records, the first
+ * min(*count, capacity) valid, device order) and its counter.  GDP_ERR_STATE before the buffer
+ * exists (first gdp_detect_extrema or gdp_set_keypoint_capacity). */
+int gdp_device_keypoints(const gdp_ctx* ctx, int b, const gdp_keypoint** records, const uint32_t** count);
+
 /* ---- output --------------------------------------------------------------------------------
  * The blocking copies below are ordered after work on the context's OWN stream; if a build was
  * launched on another stream, synchronize that stream first. */

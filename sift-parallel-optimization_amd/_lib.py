@@ -110,6 +110,11 @@ SIGNATURES = {
                                          ctypes.POINTER(ctypes.c_uint64)]),
     "gdp_upload_image_written": (_c_int, [_p, _c_int, _p]),
     "gdp_generate_dog_mirrored_written": (_c_int, [_p, _c_int, _p]),
+    "gdp_set_keypoint_capacity": (_c_int, [_p, _c_size]),
+    "gdp_detect_extrema": (_c_int, [_p, ctypes.c_float, ctypes.c_float, _p]),
+    "gdp_keypoint_count": (_c_int, [_p, _c_int, ctypes.POINTER(_c_size)]),
+    "gdp_download_keypoints": (_c_int, [_p, _c_int, _p, _c_size, ctypes.POINTER(_c_size), ctypes.POINTER(_c_size)]),
+    "gdp_device_keypoints": (_c_int, [_p, _c_int, _pp, _pp]),
     "gdp_checksum": (_c_int, [_p, _c_int, ctypes.POINTER(ctypes.c_uint64)]),
     "gdp_get_taps": (_c_int, [_p, _c_int, _c_int, _c_int, _p]),
     "gdp_set_window_centre": (_c_int, [_p, _c_int]),

@@ -52,6 +52,7 @@ namespace {
 #include "gdp_build.inc"
 #include "gdp_inplace.inc"
 #include "gdp_conv.inc"
+#include "gdp_extrema.inc"
 #include "gdp_util.inc"
 #include "gdp_track.inc"
 
@@ -161,6 +162,10 @@ struct gdp_ctx {
     hipStream_t st_up = nullptr, st_down = nullptr;
     std::vector<hipEvent_t> ev_mirror;
     unsigned long long* d_sum = nullptr;
+    // gdp_detect_extrema: [batch][kp_capacity] records and [batch] counters, allocated on first use
+    gdp_keypoint* d_kp = nullptr;
+    uint32_t* d_kp_count = nullptr;
+    size_t kp_capacity = 65536;   // gdp_set_keypoint_capacity: records per image
     std::vector<float> h_taps;
     long long in_pitch_own = 0, in_img_stride_own = 0;
     hipStream_t stream = nullptr;
@@ -991,6 +996,10 @@ int gdp_create_band(gdp_ctx** out, int H, int W, int S, int O, int batch, int ro
         g.lt_blk[o + 1] = g.lt_blk[o] + (unsigned)(((long long)og.rows + kLtRows - 1) / kLtRows * ((og.gpr + 63) / 64));
         g.cv_tiles_c[o] = (og.cols + kCvTW - 1) / kCvTW;
         g.cv_blk[o + 1] = g.cv_blk[o] + (unsigned)(((long long)og.rows + kCvTH - 1) / kCvTH * g.cv_tiles_c[o]);
+        // extrema detection: candidates are rows 1..rows-2, columns 1..cols-2 (none under 3 x 3)
+        const bool ex_any = og.rows >= 3 && og.cols >= 3;
+        g.ex_strips[o] = ex_any ? (og.gpr + kExStrip - 1) / kExStrip : 0;
+        g.ex_blk[o + 1] = g.ex_blk[o] + (unsigned)(ex_any ? ((long long)og.rows - 2 + kExRows - 1) / kExRows * g.ex_strips[o] : 0);
     }
     g.pyr_stride = round_up(lev_off, kLevelAlign);
     c->img_floats = g.pyr_stride;
@@ -1135,6 +1144,8 @@ void gdp_destroy(gdp_ctx* c) {
     if (c->st_up) (void)hipStreamDestroy(c->st_up);
     if (c->st_down) (void)hipStreamDestroy(c->st_down);
     if (c->d_sum) (void)hipFree(c->d_sum);
+    if (c->d_kp) (void)hipFree(c->d_kp);
+    if (c->d_kp_count) (void)hipFree(c->d_kp_count);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -2458,6 +2469,128 @@ int gdp_checksum(gdp_ctx* c, int b, uint64_t* out) try {
     GDP_HIP(c, hipMemcpyAsync(&v, c->d_sum, sizeof v, hipMemcpyDeviceToHost, c->stream));
     GDP_HIP(c, hipStreamSynchronize(c->stream));
     *out = v;
+    return GDP_OK;
+} GDP_ABI_CATCH(c)
+
+// ---- extension: scale-space extrema (keypoints) on the current pyramid (gdp_extrema.inc) --------
+static int ensure_keypoints(gdp_ctx* c) {
+    if (c->d_kp && c->d_kp_count) return GDP_OK;
+    const size_t batch = (size_t)c->geom.batch;
+    hipError_t e = hipSuccess;
+    if (!c->d_kp) e = hipMalloc(reinterpret_cast<void**>(&c->d_kp), c->kp_capacity * batch * sizeof(gdp_keypoint));
+    if (e == hipSuccess && !c->d_kp_count) {
+        e = hipMalloc(reinterpret_cast<void**>(&c->d_kp_count), batch * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemset(c->d_kp_count, 0, batch * sizeof(uint32_t));
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return c->status(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, "keypoint buffer (%zu records x %zu images): %s",
+                         c->kp_capacity, batch, hipGetErrorString(e));
+    }
+    return GDP_OK;
+}
+
+int gdp_set_keypoint_capacity(gdp_ctx* c, size_t per_image) try {
+    if (!c) return GDP_ERR_ARG;
+    if (per_image == 0 || per_image > (SIZE_MAX / sizeof(gdp_keypoint)) / (size_t)c->geom.batch)
+        return c->status(GDP_ERR_ARG, "gdp_set_keypoint_capacity: capacity must be > 0 and fit the address space");
+    if (per_image == c->kp_capacity && c->d_kp) return GDP_OK;
+    GDP_HIP(c, hipSetDevice(c->device));
+    if (c->d_kp) {
+        // a configuration-time event like a geometry change: no launch in flight may still write
+        // the old buffer
+        GDP_HIP(c, hipDeviceSynchronize());
+        GDP_HIP(c, hipFree(c->d_kp));
+        c->d_kp = nullptr;
+    }
+    c->kp_capacity = per_image;
+    if (c->d_kp_count) {  // the old records are gone: nothing found until the next detection
+        GDP_HIP(c, hipMemsetAsync(c->d_kp_count, 0, (size_t)c->geom.batch * sizeof(uint32_t), c->stream));
+        GDP_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return ensure_keypoints(c);
+} GDP_ABI_CATCH(c)
+
+int gdp_detect_extrema(gdp_ctx* c, float contrast_threshold, float edge_ratio, void* stream) try {
+    if (!c) return GDP_ERR_ARG;
+    if (!(contrast_threshold >= 0.0f))
+        return c->status(GDP_ERR_ARG, "gdp_detect_extrema: contrast_threshold must be >= 0");
+    if (edge_ratio != 0.0f && !(edge_ratio >= 1.0f && std::isfinite(edge_ratio)))
+        return c->status(GDP_ERR_ARG, "gdp_detect_extrema: edge_ratio must be 0 (no edge test) or finite and >= 1");
+    const Geom& g = c->geom;
+    if (g.in_row0 != 0 || g.in_rows != g.H)
+        return c->status(GDP_ERR_STATE, "gdp_detect_extrema: a row band does not hold its candidates' neighbours "
+                                        "across the band edges; detect on a whole-image context");
+    unsigned long long px = 0;
+    for (int o = 0; o < g.O; ++o) px += (unsigned long long)g.oct[o].rows * g.oct[o].cols;
+    if ((unsigned long long)g.S * px >= (1ull << 32))
+        return c->status(GDP_ERR_ARG, "gdp_detect_extrema: S x pixels per image must stay below 2^32 (the 32-bit counter)");
+    GDP_HIP(c, hipSetDevice(c->device));
+    const int rc = ensure_keypoints(c);
+    if (rc != GDP_OK) return rc;
+    hipStream_t st = c->pick(stream);
+    GDP_HIP(c, hipMemsetAsync(c->d_kp_count, 0, (size_t)g.batch * sizeof(uint32_t), st));
+    if (g.S == 0 || g.ex_blk[g.O] == 0) return GDP_OK;
+    // S <= 3: every candidate level in one pass over the S + 2 levels; above, chunks of 3
+    const int ns = std::min(g.S, 3);
+    const unsigned long long nchunks = (unsigned long long)(g.S + ns - 1) / ns;
+    const unsigned long long units = (unsigned long long)g.ex_blk[g.O] * nchunks * g.batch;
+    if (units >= (1ull << 32)) return c->status(GDP_ERR_ARG, "gdp_detect_extrema: too large for one launch (split the batch)");
+    const unsigned grid = (unsigned)((units + kExWaves - 1) / kExWaves);
+    auto kern = ns == 1 ? k_extrema<1> : ns == 2 ? k_extrema<2> : k_extrema<3>;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kExWaves), 0, st, c->d_geom, c->d_out, reinterpret_cast<uint4*>(c->d_kp),
+                       c->d_kp_count, (unsigned long long)c->kp_capacity, contrast_threshold, edge_ratio, (unsigned)nchunks);
+    GDP_HIP(c, hipGetLastError());
+    return GDP_OK;
+} GDP_ABI_CATCH(c)
+
+int gdp_keypoint_count(gdp_ctx* c, int b, size_t* found) try {
+    if (!c || !found || b < 0 || b >= c->geom.batch)
+        return c ? c->status(GDP_ERR_ARG, "gdp_keypoint_count: bad argument") : GDP_ERR_ARG;
+    *found = 0;
+    if (!c->d_kp_count) return GDP_OK;  // no detection has run
+    GDP_HIP(c, hipSetDevice(c->device));
+    uint32_t n = 0;
+    GDP_HIP(c, hipMemcpyAsync(&n, c->d_kp_count + b, sizeof n, hipMemcpyDeviceToHost, c->stream));
+    GDP_HIP(c, hipStreamSynchronize(c->stream));
+    *found = n;
+    return GDP_OK;
+} GDP_ABI_CATCH(c)
+
+int gdp_download_keypoints(gdp_ctx* c, int b, gdp_keypoint* host, size_t capacity, size_t* stored, size_t* found) try {
+    if (!c || b < 0 || b >= c->geom.batch || (!host && capacity))
+        return c ? c->status(GDP_ERR_ARG, "gdp_download_keypoints: bad argument") : GDP_ERR_ARG;
+    if (stored) *stored = 0;
+    size_t total = 0;
+    const int rc = gdp_keypoint_count(c, b, &total);
+    if (rc != GDP_OK) return rc;
+    if (found) *found = total;
+    const size_t n = std::min(total, std::min(c->kp_capacity, capacity));
+    if (n == 0) return GDP_OK;
+    GDP_SETTLE(c, "gdp_download_keypoints", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint)); });
+    GDP_HIP(c, hipMemcpyAsync(track_dma_ptr(host), c->d_kp + (size_t)b * c->kp_capacity, n * sizeof(gdp_keypoint),
+                              hipMemcpyDeviceToHost, c->stream));
+    GDP_HIP(c, hipStreamSynchronize(c->stream));
+    // the device order depends on the waves' timing; (octave, scale, row, col) is unique per record
+    std::sort(host, host + n, [](const gdp_keypoint& p, const gdp_keypoint& q) {
+        if (p.octave != q.octave) return p.octave < q.octave;
+        if (p.scale != q.scale) return p.scale < q.scale;
+        if (p.row != q.row) return p.row < q.row;
+        return p.col < q.col;
+    });
+    if (stored) *stored = n;
+    return GDP_OK;
+} GDP_ABI_CATCH(c)
+
+int gdp_device_keypoints(const gdp_ctx* c, int b, const gdp_keypoint** records, const uint32_t** count) try {
+    if (!c || b < 0 || b >= c->geom.batch) return GDP_ERR_ARG;
+    if (!c->d_kp || !c->d_kp_count) {
+        const_cast<gdp_ctx*>(c)->status(GDP_ERR_STATE, "gdp_device_keypoints: no keypoint buffer yet (run gdp_detect_extrema "
+                                                       "or gdp_set_keypoint_capacity first)");
+        return GDP_ERR_STATE;
+    }
+    if (records) *records = c->d_kp + (size_t)b * c->kp_capacity;
+    if (count) *count = c->d_kp_count + b;
     return GDP_OK;
 } GDP_ABI_CATCH(c)
 

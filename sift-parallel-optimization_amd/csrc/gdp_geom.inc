@@ -123,6 +123,9 @@ struct Geom {
     unsigned bk_blk[kMaxOct + 1];  // convolution block tiles (k_conv_blk): prefix over octaves of
                                    // T-row x 240-column tiles (same octaves as the sweep)
     int bk_strips_c[kMaxOct];      // convolution block tiles: tile columns per octave
+    unsigned ex_blk[kMaxOct + 1];  // extrema detection (k_extrema): prefix over octaves of wave units,
+                                   // kExRows candidate rows x kExStrip groups (0 for octaves under 3 x 3)
+    int ex_strips[kMaxOct];        // extrema detection: strips per octave
 };
 
 typedef float f4 __attribute__((ext_vector_type(4)));

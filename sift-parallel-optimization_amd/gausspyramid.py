@@ -54,6 +54,22 @@ def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data)
 
 
+# struct gdp_keypoint (include/gdp.h): one 16-byte record per keypoint
+KEYPOINT_DTYPE = np.dtype({"names": ["octave", "scale", "kind", "row", "col", "value"],
+                           "formats": [np.uint16, np.uint8, np.int8, np.int32, np.int32, np.float32],
+                           "offsets": [0, 2, 3, 4, 8, 12], "itemsize": 16})
+
+
+class Keypoints(np.ndarray):
+    """A KEYPOINT_DTYPE array of the stored records with `found`, the number the detection counted
+    (larger than len() when the context's capacity was too small)."""
+
+    found = 0
+
+    def __array_finalize__(self, obj):
+        self.found = getattr(obj, "found", 0)
+
+
 GDP_STREAM_NULL = 1  # include/gdp.h: selects HIP's default (null) stream
 
 
@@ -107,6 +123,7 @@ class PyramidContext:
             check(L.gdp_level_dims(self._ctx, o, ctypes.byref(r), ctypes.byref(c), ctypes.byref(f)), self._ctx)
             self._dims.append((r.value, c.value, f.value))
         self._bound = None  # keeps a caller's device input alive
+        self._kp_capacity = 65536  # gdp_set_keypoint_capacity's default
         self.input_format = "i32"
         if input_format != "i32":
             self.set_input_format(input_format)
@@ -392,6 +409,42 @@ class PyramidContext:
         check(lib().gdp_checksum(self._ctx, int(b), ctypes.byref(v)), self._ctx)
         return v.value
 
+    # ------------------------------------------------------------------ keypoints (extension)
+    def set_keypoint_capacity(self, n):
+        """Records kept per image by detect_extrema (default 65536); reallocates the buffer."""
+        check(lib().gdp_set_keypoint_capacity(self._ctx, int(n)), self._ctx)
+        self._kp_capacity = int(n)
+
+    def detect_extrema(self, contrast=0.0, edge_ratio=0.0, stream=None):
+        """Find the strict scale-space extrema of the CURRENT pyramid's levels 0..S+1 on the device
+        (gdp_detect_extrema: |value| > contrast, and the edge test when edge_ratio != 0);
+        asynchronous on `stream`, one launch for every image and octave."""
+        check(lib().gdp_detect_extrema(self._ctx, float(contrast), float(edge_ratio), _stream_handle(stream)),
+              self._ctx)
+
+    def keypoint_count(self, b=0):
+        """Keypoints the last detection found in image b (blocking; may exceed the capacity)."""
+        n = ctypes.c_size_t()
+        check(lib().gdp_keypoint_count(self._ctx, int(b), ctypes.byref(n)), self._ctx)
+        return n.value
+
+    def keypoints(self, b=0):
+        """The stored records of image b as a KEYPOINT_DTYPE array sorted by (octave, scale, row,
+        col) (blocking); its `found` attribute is keypoint_count(b)."""
+        out = np.zeros(min(self.keypoint_count(b), self._kp_capacity), KEYPOINT_DTYPE)
+        stored, found = ctypes.c_size_t(), ctypes.c_size_t()
+        check(lib().gdp_download_keypoints(self._ctx, int(b), _ptr(out) if out.size else None, out.size,
+                                           ctypes.byref(stored), ctypes.byref(found)), self._ctx)
+        out = out[:stored.value].view(Keypoints)
+        out.found = found.value
+        return out
+
+    def device_keypoints(self, b=0):
+        """(device address of image b's records, device address of its uint32 counter)."""
+        recs, count = ctypes.c_void_p(), ctypes.c_void_p()
+        check(lib().gdp_device_keypoints(self._ctx, int(b), ctypes.byref(recs), ctypes.byref(count)), self._ctx)
+        return recs.value, count.value
+
     def device_level_ptr(self, b, o, s):
         return lib().gdp_device_level(self._ctx, int(b), int(o), int(s))
 
@@ -512,6 +565,15 @@ class GaussPyramid:
             self._ctx.generate_dog()
         self._fresh = False
         self._refresh()
+
+    def DetectExtrema(self, contrast=0.0, edge_ratio=0.0):
+        """Extension (no reference counterpart): the strict scale-space extrema of the current
+        pyramid, found on the device (PyramidContext.detect_extrema), as a KEYPOINT_DTYPE array
+        sorted by (octave, scale, row, col).  Host edits to GaussPy are detected on; the pyramid is
+        not changed, so nothing is refreshed or downloaded but the records."""
+        self.SyncDevice()
+        self._ctx.detect_extrema(contrast, edge_ratio)
+        return self._ctx.keypoints(0)
 
     def output(self, file=None):
         """:89-104 — print scale 0 of each octave (space separated) and an `==` separator row."""
