@@ -1,143 +1,13 @@
 """On-device scale-space extrema (gdp_detect_extrema) against a numpy float32 oracle that implements
 the rules of include/gdp.h literally.  The result is a set and is compared exactly: position, kind
 and the bits of the value.  Most cases run on UPLOADED pyramids, independent of any build kernel."""
-import functools
-
 import numpy as np
 import pytest
 
+from extrema_oracle import (BIG, ODD, F, as_set, assert_sorted, detect, normal_pyramid, np_extrema, octave_levels,
+                            packed_size, smooth_pyramid, tie_pyramid, want)
+
 pytestmark = pytest.mark.gpu
-
-F = np.float32
-
-
-# ---------------------------------------------------------------------------------------------
-# the oracle
-# ---------------------------------------------------------------------------------------------
-def octave_levels(packed, H, W, S, O):
-    """Views [S+3][rows][cols] of every octave of a packed [o][s][rows][cols] pyramid."""
-    out, off = [], 0
-    for o in range(O):
-        r, c = H >> o, W >> o
-        out.append(packed[off:off + (S + 3) * r * c].reshape(S + 3, r, c))
-        off += (S + 3) * r * c
-    assert off == packed.size
-    return out
-
-
-def np_extrema(packed, H, W, S, O, contrast=0.0, edge_ratio=0.0):
-    """(set of (octave, scale, kind, row, col, value bits), contrast-passing extrema before the
-    edge test)."""
-    found, before_edge = set(), 0
-    er = F(edge_ratio)
-    with np.errstate(all="ignore"):
-        for o, D in enumerate(octave_levels(packed, H, W, S, O)):
-            rows, cols = D.shape[1:]
-            if S == 0 or rows < 3 or cols < 3:
-                continue
-            for s in range(1, S + 1):  # level S+2 is never read
-                v = D[s, 1:-1, 1:-1]
-                gt = np.ones(v.shape, bool)
-                lt = np.ones(v.shape, bool)
-                for ds in (-1, 0, 1):
-                    for dr in (-1, 0, 1):
-                        for dc in (-1, 0, 1):
-                            if (ds, dr, dc) != (0, 0, 0):
-                                n = D[s + ds, 1 + dr:rows - 1 + dr, 1 + dc:cols - 1 + dc]
-                                gt &= v > n
-                                lt &= v < n
-                keep = (gt | lt) & (np.abs(v) > F(contrast))
-                before_edge += int(keep.sum())
-                if edge_ratio != 0:
-                    d = lambda dr, dc: D[s, 1 + dr:rows - 1 + dr, 1 + dc:cols - 1 + dc]  # noqa: E731
-                    dxx = (d(0, 1) + d(0, -1)) - F(2) * v
-                    dyy = (d(1, 0) + d(-1, 0)) - F(2) * v
-                    dxy = ((d(1, 1) - d(1, -1)) - (d(-1, 1) - d(-1, -1))) * F(0.25)
-                    tr = dxx + dyy
-                    det = dxx * dyy - dxy * dxy
-                    assert det.dtype == np.float32 and tr.dtype == np.float32
-                    keep &= (det > F(0)) & ((tr * tr) * er < ((er + F(1)) * (er + F(1))) * det)
-                for r, c in zip(*np.nonzero(keep)):
-                    val = v[r, c]
-                    found.add((o, s, 1 if gt[r, c] else -1, int(r) + 1, int(c) + 1, int(val.view(np.uint32))))
-    return found, before_edge
-
-
-def as_set(kp):
-    got = {(int(k["octave"]), int(k["scale"]), int(k["kind"]), int(k["row"]), int(k["col"]),
-            int(k["value"].view(np.uint32))) for k in kp}
-    assert len(got) == len(kp), "duplicate records"
-    return got
-
-
-def assert_sorted(kp):
-    keys = [(int(k["octave"]), int(k["scale"]), int(k["row"]), int(k["col"])) for k in kp]
-    assert keys == sorted(keys)
-
-
-def packed_size(H, W, S, O):
-    return sum((S + 3) * (H >> o) * (W >> o) for o in range(O))
-
-
-def detect(pkg, packed, H, W, S, octaves=0, contrast=0.0, edge_ratio=0.0, capacity=None):
-    with pkg.PyramidContext(H, W, S=S, octaves=octaves) as ctx:
-        if capacity:
-            ctx.set_keypoint_capacity(capacity)
-        ctx.upload_pyramid(packed)
-        ctx.detect_extrema(contrast, edge_ratio)
-        kp = ctx.keypoints(0)
-        assert kp.found == ctx.keypoint_count(0)
-        assert_sorted(kp)
-        return kp
-
-
-# ---------------------------------------------------------------------------------------------
-# shared inputs (computed once, never modified)
-# ---------------------------------------------------------------------------------------------
-BIG = (200, 520, 2, 8)     # all 8 octaves; ~20 k keypoints: every seam of any tiling is hit
-ODD = (37, 100, 3, 6)      # odd widths (octave-2 cols = 25), unaligned rows, 4x12 / 2x6 / 1x3 octaves
-
-
-@functools.lru_cache(maxsize=None)
-def normal_pyramid(shape):
-    H, W, S, O = shape
-    p = np.random.default_rng(7).standard_normal(packed_size(H, W, S, O), dtype=np.float32)
-    p.setflags(write=False)
-    return p
-
-
-@functools.lru_cache(maxsize=None)
-def tie_pyramid(shape):
-    """Integers in [-3, 3] (ties everywhere) with a few hundred NaN, +-inf, +-0 and denormals."""
-    H, W, S, O = shape
-    rng = np.random.default_rng(7)
-    p = rng.integers(-3, 4, packed_size(H, W, S, O)).astype(np.float32)
-    special = np.array([np.nan, -np.nan, np.inf, -np.inf, 0.0, -0.0, 1e-45, -1e-45, 1e-39, -1e-39], np.float32)
-    where = rng.choice(p.size, 400, replace=False)
-    p[where] = special[rng.integers(0, special.size, where.size)]
-    p.setflags(write=False)
-    return p
-
-
-@functools.lru_cache(maxsize=None)
-def smooth_pyramid(shape):
-    """normal_pyramid box-filtered along rows with 5 taps (edge rows repeated)."""
-    H, W, S, O = shape
-    out = np.empty_like(normal_pyramid(shape))
-    for src, dst in zip(octave_levels(normal_pyramid(shape), H, W, S, O), octave_levels(out, H, W, S, O)):
-        pad = np.pad(src, ((0, 0), (0, 0), (2, 2)), mode="edge")
-        acc = np.zeros_like(src)
-        for k in range(5):
-            acc = acc + pad[:, :, k:k + src.shape[2]]
-        dst[...] = acc * F(0.2)
-    out.setflags(write=False)
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def want(kind, shape, contrast=0.0, edge_ratio=0.0):
-    src = {"normal": normal_pyramid, "tie": tie_pyramid, "smooth": smooth_pyramid}[kind](shape)
-    return np_extrema(src, *shape, contrast=contrast, edge_ratio=edge_ratio)
 
 
 # ---------------------------------------------------------------------------------------------
