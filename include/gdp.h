@@ -249,8 +249,18 @@ int gdp_device_keypoints(const gdp_ctx* ctx, int b, const gdp_keypoint** records
 /* ---- output --------------------------------------------------------------------------------
  * The blocking copies below are ordered after work on the context's OWN stream; if a build was
  * launched on another stream, synchronize that stream first. */
-/* Device pointer to level (o, s) of image b: rows x cols float32, row-major, dense. */
+/* Device pointer to level (o, s) of image b: rows x cols float32, row-major, dense.  The pointer
+ * is const: read through it freely.  Whoever casts the const away and WRITES through it (a
+ * collective receiving into the pyramid, a caller's own kernel) calls gdp_pyramid_written on this
+ * context before its next gdp_build — libgdp tracks its own writers, not foreign ones, and a build
+ * on a pyramid it believes untouched keeps the input-independent zeros an earlier build stored
+ * (GDP_TUNE_KEEP_ZEROS). */
 const float* gdp_device_level(const gdp_ctx* ctx, int b, int octave, int scale);
+/* Tell the context that image b's pyramid (b < 0: every image's) was, or is about to be, written
+ * by something other than libgdp: the next gdp_build stores every byte again.  Host-side flag
+ * only (no device work, no synchronisation); order the write itself against the build as for any
+ * two device operations. */
+int gdp_pyramid_written(gdp_ctx* ctx, int b);
 /* Copy level (o, s) of image b to a dense host array (blocking). */
 int gdp_download_level(gdp_ctx* ctx, int b, int octave, int scale, float* host);
 /* Copy level (o, s) of image b into host row pointers — materialises the reference's
@@ -464,9 +474,19 @@ enum {
     GDP_TUNE_INPLACE_PACE = 19, /* the same for the in-place re-entry (gdp_generate_dog, k_levels;
                                    default -1): its own field, so tuning the build's pacing never
                                    changes the in-place passes' speed */
-    GDP_TUNE_PYRAMID_CHUNK_KB = 20 /* read-only: how the context-owned pyramid is backed — KiB per
+    GDP_TUNE_PYRAMID_CHUNK_KB = 20, /* read-only: how the context-owned pyramid is backed — KiB per
                                       separately created physical piece (default 2 MiB, at most
                                       4096 pieces), -1 one piece per image, 0 one hipMalloc */
+    GDP_TUNE_KEEP_ZEROS = 21,   /* 1 (default): a gdp_build into the context-owned pyramid that
+                                   follows another one, with no pyramid writer in between, does not
+                                   store the S+2 DoG levels outside the windows' support again —
+                                   they are +0 for any input and already there; level S+2 and the
+                                   support are stored as ever.  The same bits either way; 0 = every
+                                   build stores every byte.  A launch-time flag: no drain */
+    GDP_TUNE_ZEROS_CLEAN = 22   /* read-only: 1 while the next gdp_build may skip those stores (set
+                                   by a gdp_build into the context-owned pyramid, cleared by every
+                                   call that writes, moves or rebinds pyramid memory and by
+                                   gdp_pyramid_written) */
 };
 int gdp_set_tuning(gdp_ctx* ctx, int key, int value);
 /* The build-kernel variant ids this library holds (GDP_TUNE_VARIANT values): writes up to
@@ -489,7 +509,10 @@ void* gdp_stream(const gdp_ctx* ctx);          /* the context's own hipStream_t 
 const char* gdp_last_error(const gdp_ctx* ctx); /* ctx may be NULL: last create() failure */
 const char* gdp_status_string(int status);
 /* Time `iters` back-to-back gdp_build launches on `stream` with HIP events recorded on that same
- * stream; writes the total milliseconds.  Used by bench.py for the per-launch kernel time. */
+ * stream; writes the total milliseconds.  Used by bench.py for the per-launch kernel time.  One
+ * untimed build runs first, so every timed launch finds the pyramid in the same state (clean, with
+ * GDP_TUNE_KEEP_ZEROS: the steady state of a context that is built again and again; the cost of a
+ * first build is what GDP_TUNE_KEEP_ZEROS = 0 times).  gdp_autotune times its candidates this way. */
 int gdp_time_builds(gdp_ctx* ctx, int iters, void* stream, float* total_ms);
 
 #ifdef __cplusplus

@@ -30,6 +30,8 @@ GDP_TUNE_STORE_PACE = 17
 GDP_TUNE_CONV_PACE = 18
 GDP_TUNE_INPLACE_PACE = 19
 GDP_TUNE_PYRAMID_CHUNK_KB = 20
+GDP_TUNE_KEEP_ZEROS = 21
+GDP_TUNE_ZEROS_CLEAN = 22
 
 
 class GdpError(RuntimeError):
@@ -81,6 +83,7 @@ SIGNATURES = {
     "gdp_build_subset": (_c_int, [_p, _p]),
     "gdp_generate_dog_subset": (_c_int, [_p, _p]),
     "gdp_device_level": (_p, [_p, _c_int, _c_int, _c_int]),
+    "gdp_pyramid_written": (_c_int, [_p, _c_int]),
     "gdp_download_level": (_c_int, [_p, _c_int, _c_int, _c_int, _p]),
     "gdp_download_level_rows": (_c_int, [_p, _c_int, _c_int, _c_int, _p]),
     "gdp_download_level_range": (_c_int, [_p, _c_int, _c_int, _c_int, _c_int, _c_int, _p]),

@@ -141,6 +141,15 @@ struct gdp_ctx {
     bool conv_perm_dirty = true;
     int conv_perm_kernel = -1;       // the conv kernel d_conv_perm was built for (its block prefix)
     float* d_out_own = nullptr;   // context-owned pyramid (d_out may point at caller memory)
+    // The context-owned pyramid holds, outside the windows' support, the +0 a build stores into the
+    // S+2 DoG levels for ANY input: set by a full build into d_out_own (launch_build), cleared by
+    // everything else that can write or move pyramid memory (pyramid_written; default-deny: every
+    // non-const export clears it unless it carries GDP_READS_PYRAMID).  While set, the next build
+    // passes k_build `keep` and skips those stores.  Changed at ENQUEUE time on the host: correct
+    // under the ordering a caller already owes between a writer and a later build on another
+    // stream (the build must be ordered after the writer for its own stores to survive).
+    bool zeros_clean = false;
+    int keep_zeros = 1;           // GDP_TUNE_KEEP_ZEROS: 0 = every build stores every byte
     long long img_floats = 0;     // one image's dense extent (pyr_stride may be larger: GDP_IMAGE_STRIDE_MB)
     // GDP_SPREAD_VMM: the pyramid as one reserved address range with separately created physical
     // chunks mapped into it (alloc_spread); each entry: handle, byte offset, bytes
@@ -263,9 +272,26 @@ int upload_geom(gdp_ctx* c) {
     return GDP_OK;
 }
 
+// Every writer of pyramid memory (and everything that moves or rebinds it) passes through here:
+// the next build stores every byte again.
+inline void pyramid_written(gdp_ctx* c) {
+    if (c) c->zeros_clean = false;
+}
+// First statement of every export that takes a non-const context: GDP_WRITES_PYRAMID unless the
+// export provably leaves the context's pyramid alone (GDP_READS_PYRAMID — the explicit read-only
+// list; tests/test_keep_zeros_abi.py checks that every such export carries one of the two, so a
+// new writer invalidates by default).
+#define GDP_WRITES_PYRAMID(ctx) pyramid_written(ctx)
+#define GDP_READS_PYRAMID(ctx) ((void)(ctx))
+#define GDP_BUILDS_PYRAMID(ctx) ((void)(ctx))  // gdp_build and the build timers: launch_build keeps the flag itself
+
 int launch_build(gdp_ctx* c, hipStream_t st, bool subset = false) {
     const Geom& g = c->geom;
     const long long units = (long long)g.tiles_total + g.tail_units;
+    // the flag as this launch found it; whatever happens below, a failed or subset launch leaves it clear
+    const bool own = c->d_out == c->d_out_own;
+    const int keep = (!subset && c->keep_zeros && c->zeros_clean && own) ? 1 : 0;
+    c->zeros_clean = false;
     if (units == 0) return GDP_OK;
     // default: one unit per block; GDP_TUNE_GRID / GDP_TUNE_BLOCKS_PER_CU cap it (persistent loop)
     const long long cap = c->grid_override > 0 ? c->grid_override : (c->persistent ? c->blocks_max : units);
@@ -273,8 +299,11 @@ int launch_build(gdp_ctx* c, hipStream_t st, bool subset = false) {
     const BuildVariant& v = kVariants[variant_index(c->variant)];
     auto kern = (subset ? v.ksub : v.k)[g.L == 5][c->nontemporal ? 1 : 0];
     hipLaunchKernelGGL(kern, dim3(grid), dim3(v.block), (unsigned)c->build_lds, st, c->d_geom, c->d_in, c->d_out,
-                       c->d_taps);
+                       c->d_taps, keep);
     GDP_HIP(c, hipGetLastError());
+    // a full build into the context's own pyramid leaves every DoG level outside the support +0,
+    // whichever zero-window mode ran (the full path computes the same +0)
+    c->zeros_clean = !subset && own;
     return GDP_OK;
 }
 
@@ -374,11 +403,13 @@ void fill_host_taps(gdp_ctx* c, int mode) {
 // table pointer swap, needs no geometry change).  The reference's windows underflow to +0 a few
 // σ from the centre (expf(-d²/(2σ²)) = 0 for d >= 29 at σ = 2), so on a large image almost every
 // pixel lies outside them.  `on` = 0: the ranges cover the whole octave (every group computed).
-// The ranges are computed once per context (host expf over every row and column of every octave)
-// and only copied in and out of the Geom when the knob changes.
+// The ranges are computed once per context, at its creation (host expf over every row and column
+// of every octave), and only copied in and out of the Geom when the knob changes.  OctGeom::sp_*
+// always hold them: a build on a clean pyramid (gdp_ctx::zeros_clean) skips the DoG stores outside
+// them whatever the knob says.
 void set_window_support(gdp_ctx* c, bool on) {
     Geom& g = c->geom;
-    if (on && c->support.size() != (size_t)g.O) {
+    if (c->support.size() != (size_t)g.O) {
         c->support.assign((size_t)g.O, {0, 0, 0, 0, 0});
         for (int o = 0; o < g.O; ++o) {
             auto support = [&](int length, int& lo, int& hi, float& peak) {
@@ -409,8 +440,9 @@ void set_window_support(gdp_ctx* c, bool on) {
     }
     for (int o = 0; o < g.O; ++o) {
         OctGeom& og = g.oct[o];
+        const auto& r = c->support[(size_t)o];
+        og.sp_r0 = r[0], og.sp_r1 = r[1], og.sp_c0 = r[2], og.sp_c1 = r[3];  // the keep test: knob-independent
         if (on) {
-            const auto& r = c->support[(size_t)o];
             og.nz_r0 = r[0], og.nz_r1 = r[1], og.nz_c0 = r[2], og.nz_c1 = r[3];
             og.nzi_r0 = r[4] ? r[0] : 0;
             og.nzi_r1 = r[4] ? r[1] : g.H >> o;
@@ -714,6 +746,7 @@ static void free_pyramid(gdp_ctx* c) {
     c->vmm_span = 0;
     c->d_out_own = nullptr;
     c->pyr_chunk_kb = 0;
+    c->zeros_clean = false;  // whatever backs the pyramid next holds nothing yet
 }
 
 // The pyramid's default backing (GDP_SPREAD_VMM=0 opts out): reserve its address range
@@ -1095,6 +1128,7 @@ int gdp_create_band(gdp_ctx** out, int H, int W, int S, int O, int batch, int ro
         }
     }
     c->d_out = c->d_out_own;
+    c->zeros_clean = false;  // fresh memory: the first build stores every byte
     if ((e = hipMalloc(&c->d_sum, sizeof(unsigned long long))) != hipSuccess) return hip_fail(e, "hipMalloc(sum)");
     c->d_in = c->d_in_own;
     if ((e = hipMemcpy(c->d_taps, c->h_taps.data(), c->h_taps.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
@@ -1218,11 +1252,13 @@ int bind_input(gdp_ctx* c, const void* base, size_t pitch, size_t image_stride, 
 }  // namespace
 
 int gdp_set_input_host(gdp_ctx* c, int b, const int32_t* base, size_t pitch, void* stream) try {
+    GDP_READS_PYRAMID(c);
     if (c) GDP_SETTLE(c, "gdp_set_input_host", [&](auto&& f) { f(base, pitch * 4 * (size_t)c->geom.in_rows); });
     return upload_input(c, b, base, pitch, GDP_INPUT_I32, stream, "gdp_set_input_host");
 } GDP_ABI_CATCH(c)
 
 int gdp_set_input_host_u8(gdp_ctx* c, int b, const uint8_t* base, size_t pitch, void* stream) try {
+    GDP_READS_PYRAMID(c);
     if (c) GDP_SETTLE(c, "gdp_set_input_host_u8", [&](auto&& f) { f(base, pitch * (size_t)c->geom.in_rows); });
     return upload_input(c, b, base, pitch, GDP_INPUT_U8, stream, "gdp_set_input_host_u8");
 } GDP_ABI_CATCH(c)
@@ -1231,6 +1267,7 @@ static int ensure_stage(gdp_ctx* c, size_t floats);
 static void parallel_rows(size_t nrows, size_t floats, int threads, const std::function<void(size_t, size_t)>& fn);
 
 int gdp_set_input_rows(gdp_ctx* c, int b, const int32_t* const* rows, void* stream) try {
+    GDP_READS_PYRAMID(c);
     if (!c || !rows || b < 0 || b >= c->geom.batch) return c ? c->status(GDP_ERR_ARG, "gdp_set_input_rows: bad argument") : GDP_ERR_ARG;
     if (c->d_in != c->d_in_own) return c->status(GDP_ERR_STATE, "input is bound to caller device memory");
     if (c->geom.in_fmt != GDP_INPUT_I32)
@@ -1264,14 +1301,17 @@ int gdp_set_input_rows(gdp_ctx* c, int b, const int32_t* const* rows, void* stre
 } GDP_ABI_CATCH(c)
 
 int gdp_set_input_device(gdp_ctx* c, const int32_t* base, size_t pitch, size_t image_stride) try {
+    GDP_READS_PYRAMID(c);
     return bind_input(c, base, pitch, image_stride, GDP_INPUT_I32, "gdp_set_input_device");
 } GDP_ABI_CATCH(c)
 
 int gdp_set_input_device_u8(gdp_ctx* c, const uint8_t* base, size_t pitch, size_t image_stride) try {
+    GDP_READS_PYRAMID(c);
     return bind_input(c, base, pitch, image_stride, GDP_INPUT_U8, "gdp_set_input_device_u8");
 } GDP_ABI_CATCH(c)
 
 int gdp_set_input_format(gdp_ctx* c, int fmt) try {
+    GDP_READS_PYRAMID(c);
     if (!c || (fmt != GDP_INPUT_I32 && fmt != GDP_INPUT_U8)) return c ? c->status(GDP_ERR_ARG, "unknown input format") : GDP_ERR_ARG;
     if (fmt == c->geom.in_fmt) return GDP_OK;
     GDP_HIP(c, hipSetDevice(c->device));
@@ -1301,6 +1341,7 @@ int gdp_set_input_format(gdp_ctx* c, int fmt) try {
 int gdp_get_input_format(const gdp_ctx* c) { return c ? c->geom.in_fmt : -1; }
 
 int gdp_fill_synthetic(gdp_ctx* c, uint32_t seed, long first_image, void* stream) try {
+    GDP_READS_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     const long long total = (long long)c->geom.in_rows * c->geom.W * c->geom.batch;
@@ -1314,6 +1355,7 @@ int gdp_fill_synthetic(gdp_ctx* c, uint32_t seed, long first_image, void* stream
 } GDP_ABI_CATCH(c)
 
 int gdp_build(gdp_ctx* c, void* stream) try {
+    GDP_BUILDS_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     return launch_build(c, c->pick(stream));
@@ -1344,6 +1386,7 @@ int gdp_conv_halo_rows(const gdp_ctx* c, int* above, int* below) try {
 } GDP_ABI_CATCH(c)
 
 int gdp_input_halo(gdp_ctx* c, int side, void** rows, size_t* pitch) try {
+    GDP_READS_PYRAMID(c);
     if (!c || side < 0 || side > 1 || !rows || !pitch) return c ? c->status(GDP_ERR_ARG, "gdp_input_halo: bad argument") : GDP_ERR_ARG;
     Geom& g = c->geom;
     int n[2];
@@ -1375,6 +1418,7 @@ int gdp_input_halo(gdp_ctx* c, int side, void** rows, size_t* pitch) try {
 } GDP_ABI_CATCH(c)
 
 int gdp_bind_input_halo(gdp_ctx* c, const void* above, const void* below, size_t pitch, size_t image_stride) try {
+    GDP_READS_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
     Geom& g = c->geom;
     int n[2];
@@ -1431,6 +1475,7 @@ static int conv_band_check(gdp_ctx* c) {
 }
 
 int gdp_build_gaussian(gdp_ctx* c, void* stream) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
     const Geom& g = c->geom;
     const bool band = g.in_row0 != 0 || g.in_rows != g.H;
@@ -1497,24 +1542,28 @@ int gdp_build_gaussian(gdp_ctx* c, void* stream) try {
 } GDP_ABI_CATCH(c)
 
 int gdp_init(gdp_ctx* c, void* stream) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     return launch_inplace<4>(c, 0, c->geom.O, c->pick(stream));
 } GDP_ABI_CATCH(c)
 
 int gdp_gauss_octave(gdp_ctx* c, int o, void* stream) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c || o < 0 || o >= c->geom.O) return c ? c->status(GDP_ERR_ARG, "octave out of range") : GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     return launch_inplace<1>(c, o, o + 1, c->pick(stream));
 } GDP_ABI_CATCH(c)
 
 int gdp_gauss_range(gdp_ctx* c, int ob, int oe, void* stream) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c || ob < 0 || oe > c->geom.O || ob >= oe) return c ? c->status(GDP_ERR_ARG, "octave range invalid") : GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     return launch_inplace<1>(c, ob, oe, c->pick(stream));
 } GDP_ABI_CATCH(c)
 
 int gdp_gauss_scales(gdp_ctx* c, int sb, int se, int ob, int oe, void* stream) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c || ob < 0 || oe > c->geom.O || ob >= oe || sb < 0 || se > c->geom.L || sb >= se)
         return c ? c->status(GDP_ERR_ARG, "gdp_gauss_scales: scale / octave range invalid") : GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
@@ -1522,30 +1571,35 @@ int gdp_gauss_scales(gdp_ctx* c, int sb, int se, int ob, int oe, void* stream) t
 } GDP_ABI_CATCH(c)
 
 int gdp_dog_octave(gdp_ctx* c, int o, void* stream) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c || o < 0 || o >= c->geom.O) return c ? c->status(GDP_ERR_ARG, "octave out of range") : GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     return launch_inplace<2>(c, o, o + 1, c->pick(stream));
 } GDP_ABI_CATCH(c)
 
 int gdp_dog_range(gdp_ctx* c, int ob, int oe, void* stream) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c || ob < 0 || oe > c->geom.O || ob >= oe) return c ? c->status(GDP_ERR_ARG, "octave range invalid") : GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     return launch_inplace<2>(c, ob, oe, c->pick(stream));
 } GDP_ABI_CATCH(c)
 
 int gdp_generate_dog(gdp_ctx* c, void* stream) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     return launch_inplace<3>(c, 0, c->geom.O, c->pick(stream));
 } GDP_ABI_CATCH(c)
 
 int gdp_build_subset(gdp_ctx* c, void* stream) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     return launch_build(c, c->pick(stream), true);
 } GDP_ABI_CATCH(c)
 
 int gdp_generate_dog_subset(gdp_ctx* c, void* stream) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     return launch_inplace_sub<9, 1>(c, 0, c->geom.O, c->pick(stream));
@@ -1558,6 +1612,7 @@ const float* gdp_device_level(const gdp_ctx* c, int b, int o, int s) {
 }
 
 int gdp_download_level(gdp_ctx* c, int b, int o, int s, float* host) try {
+    GDP_READS_PYRAMID(c);
     if (!valid_level(c, b, o, s) || !host) return c ? c->status(GDP_ERR_ARG, "gdp_download_level: bad argument") : GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     GDP_SETTLE(c, "gdp_download_level", [&](auto&& f) { f(host, (size_t)c->geom.oct[o].rows * c->geom.oct[o].cols * 4); });
@@ -1678,6 +1733,7 @@ static int stage_download(gdp_ctx* c, const std::vector<StagePiece>& pieces) {
 }
 
 int gdp_download_level_rows(gdp_ctx* c, int b, int o, int s, float* const* rows) try {
+    GDP_READS_PYRAMID(c);
     if (!valid_level(c, b, o, s) || !rows) return c ? c->status(GDP_ERR_ARG, "gdp_download_level_rows: bad argument") : GDP_ERR_ARG;
     const OctGeom& og = c->geom.oct[o];
     if ((size_t)og.rows * og.cols == 0) return GDP_OK;
@@ -1687,6 +1743,7 @@ int gdp_download_level_rows(gdp_ctx* c, int b, int o, int s, float* const* rows)
 } GDP_ABI_CATCH(c)
 
 int gdp_download_pyramid_rows(gdp_ctx* c, int b, float* const* const* const* py) try {
+    GDP_READS_PYRAMID(c);
     if (!c || !py || b < 0 || b >= c->geom.batch)
         return c ? c->status(GDP_ERR_ARG, "gdp_download_pyramid_rows: bad argument") : GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
@@ -1707,6 +1764,7 @@ int gdp_download_pyramid_rows(gdp_ctx* c, int b, float* const* const* const* py)
 } GDP_ABI_CATCH(c)
 
 int gdp_download_level_range(gdp_ctx* c, int b, int o, int s, int first_row, int nrows, float* host) try {
+    GDP_READS_PYRAMID(c);
     if (!valid_level(c, b, o, s) || !host || first_row < 0 || nrows < 0 || first_row > c->geom.oct[o].rows ||
         nrows > c->geom.oct[o].rows - first_row)
         return c ? c->status(GDP_ERR_ARG, "gdp_download_level_range: bad argument") : GDP_ERR_ARG;
@@ -1721,6 +1779,7 @@ int gdp_download_level_range(gdp_ctx* c, int b, int o, int s, int first_row, int
 } GDP_ABI_CATCH(c)
 
 int gdp_download_pyramid(gdp_ctx* c, int b, float* host) try {
+    GDP_READS_PYRAMID(c);
     if (!c || !host || b < 0 || b >= c->geom.batch) return c ? c->status(GDP_ERR_ARG, "gdp_download_pyramid: bad argument") : GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     GDP_SETTLE(c, "gdp_download_pyramid", [&](auto&& f) { f(host, packed_pyramid_bytes(c)); });
@@ -1736,6 +1795,7 @@ int gdp_download_pyramid(gdp_ctx* c, int b, float* host) try {
 } GDP_ABI_CATCH(c)
 
 int gdp_upload_pyramid(gdp_ctx* c, int b, const float* host) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c || !host || b < 0 || b >= c->geom.batch) return c ? c->status(GDP_ERR_ARG, "gdp_upload_pyramid: bad argument") : GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     GDP_SETTLE(c, "gdp_upload_pyramid", [&](auto&& f) { f(host, packed_pyramid_bytes(c)); });
@@ -1821,6 +1881,7 @@ static int stage_upload(gdp_ctx* c, const std::vector<UpPiece>& pieces) {
 }
 
 int gdp_upload_level(gdp_ctx* c, int b, int o, int s, const float* host) try {
+    GDP_WRITES_PYRAMID(c);
     if (!valid_level(c, b, o, s) || !host) return c ? c->status(GDP_ERR_ARG, "gdp_upload_level: bad argument") : GDP_ERR_ARG;
     const OctGeom& og = c->geom.oct[o];
     if ((size_t)og.rows * og.cols == 0) return GDP_OK;
@@ -1833,6 +1894,7 @@ int gdp_upload_level(gdp_ctx* c, int b, int o, int s, const float* host) try {
 } GDP_ABI_CATCH(c)
 
 int gdp_upload_level_rows(gdp_ctx* c, int b, int o, int s, const float* const* rows) try {
+    GDP_WRITES_PYRAMID(c);
     if (!valid_level(c, b, o, s) || !rows) return c ? c->status(GDP_ERR_ARG, "gdp_upload_level_rows: bad argument") : GDP_ERR_ARG;
     const OctGeom& og = c->geom.oct[o];
     if ((size_t)og.rows * og.cols == 0) return GDP_OK;
@@ -1842,6 +1904,7 @@ int gdp_upload_level_rows(gdp_ctx* c, int b, int o, int s, const float* const* r
 } GDP_ABI_CATCH(c)
 
 int gdp_upload_pyramid_rows(gdp_ctx* c, int b, const float* const* const* const* py) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c || !py || b < 0 || b >= c->geom.batch)
         return c ? c->status(GDP_ERR_ARG, "gdp_upload_pyramid_rows: bad argument") : GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
@@ -1865,6 +1928,7 @@ int gdp_upload_pyramid_rows(gdp_ctx* c, int b, const float* const* const* const*
 } GDP_ABI_CATCH(c)
 
 int gdp_upload_image_raw(gdp_ctx* c, int b, const float* host) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c || !host || b < 0 || b >= c->geom.batch)
         return c ? c->status(GDP_ERR_ARG, "gdp_upload_image_raw: bad argument") : GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
@@ -1876,6 +1940,7 @@ int gdp_upload_image_raw(gdp_ctx* c, int b, const float* host) try {
 } GDP_ABI_CATCH(c)
 
 int gdp_get_taps(gdp_ctx* c, int axis, int o, int s, float* host) try {
+    GDP_READS_PYRAMID(c);
     if (!c || !host || o < 0 || o >= c->geom.O || s < 0 || s >= c->geom.L || (axis != 0 && axis != 1))
         return c ? c->status(GDP_ERR_ARG, "gdp_get_taps: bad argument") : GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
@@ -1895,6 +1960,7 @@ int gdp_get_taps(gdp_ctx* c, int axis, int o, int s, float* host) try {
 } GDP_ABI_CATCH(c)
 
 int gdp_set_output_device(gdp_ctx* c, float* base, size_t bytes) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
     if (!base) {
         c->d_out = c->d_out_own;
@@ -1970,6 +2036,7 @@ static int finish_download(gdp_ctx* c, const void* host, bool covers) {
 }
 
 int gdp_download_image_raw(gdp_ctx* c, int b, float* host) try {
+    GDP_READS_PYRAMID(c);
     if (!c || !host || b < 0 || b >= c->geom.batch)
         return c ? c->status(GDP_ERR_ARG, "gdp_download_image_raw: bad argument") : GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
@@ -2102,6 +2169,7 @@ static int generate_dog_mirrored(gdp_ctx* c, int b, float* host, const std::vect
 }
 
 int gdp_generate_dog_mirrored(gdp_ctx* c, int b, float* host) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c || !host || b < 0 || b >= c->geom.batch)
         return c ? c->status(GDP_ERR_ARG, "gdp_generate_dog_mirrored: bad argument") : GDP_ERR_ARG;
     GDP_SETTLE(c, "gdp_generate_dog_mirrored", [&](auto&& f) { f(host, (size_t)c->img_floats * 4); });  // the whole host image is the input
@@ -2293,6 +2361,7 @@ static TrackedMirror* track_for_image(const gdp_ctx* c, const void* host, std::v
 // their GPU work concurrent.  A buffer must not be freed or untracked by another thread during a
 // call on it — the caller's contract for any buffer it passes in.)
 int gdp_upload_image_written(gdp_ctx* c, int b, const float* host) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c || !host || b < 0 || b >= c->geom.batch)
         return c ? c->status(GDP_ERR_ARG, "gdp_upload_image_written: bad argument") : GDP_ERR_ARG;
     std::vector<std::pair<size_t, size_t>> runs;
@@ -2335,6 +2404,7 @@ int gdp_upload_image_written(gdp_ctx* c, int b, const float* host) try {
 } GDP_ABI_CATCH(c)
 
 int gdp_generate_dog_mirrored_written(gdp_ctx* c, int b, float* host) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c || !host || b < 0 || b >= c->geom.batch)
         return c ? c->status(GDP_ERR_ARG, "gdp_generate_dog_mirrored_written: bad argument") : GDP_ERR_ARG;
     std::vector<std::pair<size_t, size_t>> runs;
@@ -2364,6 +2434,7 @@ int gdp_generate_dog_mirrored_written(gdp_ctx* c, int b, float* host) try {
 
 // ---- deferred download (gdp_track.inc) ----
 int gdp_host_defer(gdp_ctx* c, int b, void* host) try {
+    GDP_READS_PYRAMID(c);
     if (!c || !host || b < 0 || b >= c->geom.batch)
         return c ? c->status(GDP_ERR_ARG, "gdp_host_defer: bad argument") : GDP_ERR_ARG;
     const size_t img_bytes = (size_t)c->img_floats * 4;
@@ -2457,6 +2528,7 @@ int gdp_host_deferred_stats(const void* host, size_t* stale_bytes, size_t* fetch
 } GDP_ABI_CATCH(nullptr)
 
 int gdp_checksum(gdp_ctx* c, int b, uint64_t* out) try {
+    GDP_READS_PYRAMID(c);
     if (!c || !out || b < 0 || b >= c->geom.batch) return c ? c->status(GDP_ERR_ARG, "gdp_checksum: bad argument") : GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     GDP_HIP(c, hipMemsetAsync(c->d_sum, 0, sizeof(unsigned long long), c->stream));
@@ -2491,6 +2563,7 @@ static int ensure_keypoints(gdp_ctx* c) {
 }
 
 int gdp_set_keypoint_capacity(gdp_ctx* c, size_t per_image) try {
+    GDP_READS_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
     if (per_image == 0 || per_image > (SIZE_MAX / sizeof(gdp_keypoint)) / (size_t)c->geom.batch)
         return c->status(GDP_ERR_ARG, "gdp_set_keypoint_capacity: capacity must be > 0 and fit the address space");
@@ -2512,6 +2585,7 @@ int gdp_set_keypoint_capacity(gdp_ctx* c, size_t per_image) try {
 } GDP_ABI_CATCH(c)
 
 int gdp_detect_extrema(gdp_ctx* c, float contrast_threshold, float edge_ratio, void* stream) try {
+    GDP_READS_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
     if (!(contrast_threshold >= 0.0f))
         return c->status(GDP_ERR_ARG, "gdp_detect_extrema: contrast_threshold must be >= 0");
@@ -2545,6 +2619,7 @@ int gdp_detect_extrema(gdp_ctx* c, float contrast_threshold, float edge_ratio, v
 } GDP_ABI_CATCH(c)
 
 int gdp_keypoint_count(gdp_ctx* c, int b, size_t* found) try {
+    GDP_READS_PYRAMID(c);
     if (!c || !found || b < 0 || b >= c->geom.batch)
         return c ? c->status(GDP_ERR_ARG, "gdp_keypoint_count: bad argument") : GDP_ERR_ARG;
     *found = 0;
@@ -2558,6 +2633,7 @@ int gdp_keypoint_count(gdp_ctx* c, int b, size_t* found) try {
 } GDP_ABI_CATCH(c)
 
 int gdp_download_keypoints(gdp_ctx* c, int b, gdp_keypoint* host, size_t capacity, size_t* stored, size_t* found) try {
+    GDP_READS_PYRAMID(c);
     if (!c || b < 0 || b >= c->geom.batch || (!host && capacity))
         return c ? c->status(GDP_ERR_ARG, "gdp_download_keypoints: bad argument") : GDP_ERR_ARG;
     if (stored) *stored = 0;
@@ -2595,6 +2671,7 @@ int gdp_device_keypoints(const gdp_ctx* c, int b, const gdp_keypoint** records, 
 } GDP_ABI_CATCH(c)
 
 int gdp_set_window_centre(gdp_ctx* c, int mode) try {
+    GDP_WRITES_PYRAMID(c);
     if (!c || (mode != GDP_CENTRE_SERIAL && mode != GDP_CENTRE_INTLEN))
         return c ? c->status(GDP_ERR_ARG, "gdp_set_window_centre: mode must be GDP_CENTRE_SERIAL or GDP_CENTRE_INTLEN") : GDP_ERR_ARG;
     if (mode == c->centre_mode) return GDP_OK;
@@ -2621,6 +2698,7 @@ int gdp_set_window_centre(gdp_ctx* c, int mode) try {
 int gdp_get_window_centre(const gdp_ctx* c) { return c ? c->centre_mode : -1; }
 
 int gdp_copy_band(gdp_ctx* band, int bi, const gdp_ctx* full, int fi, void* stream) try {
+    GDP_WRITES_PYRAMID(band);
     if (!band || !full || bi < 0 || bi >= band->geom.batch || fi < 0 || fi >= full->geom.batch)
         return band ? band->status(GDP_ERR_ARG, "gdp_copy_band: bad argument") : GDP_ERR_ARG;
     const Geom &gb = band->geom, &gf = full->geom;
@@ -2642,7 +2720,14 @@ int gdp_copy_band(gdp_ctx* band, int bi, const gdp_ctx* full, int fi, void* stre
     return GDP_OK;
 } GDP_ABI_CATCH(band)
 
+int gdp_pyramid_written(gdp_ctx* c, int b) try {
+    GDP_WRITES_PYRAMID(c);  // context-granular: one image written (b >= 0) or all (b < 0), the same invalidation
+    if (!c || b >= c->geom.batch) return c ? c->status(GDP_ERR_ARG, "gdp_pyramid_written: image out of range") : GDP_ERR_ARG;
+    return GDP_OK;
+} GDP_ABI_CATCH(c)
+
 int gdp_sync(gdp_ctx* c) try {
+    GDP_READS_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     GDP_HIP(c, hipStreamSynchronize(c->stream));
@@ -2652,6 +2737,7 @@ int gdp_sync(gdp_ctx* c) try {
 void* gdp_stream(const gdp_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
 int gdp_autotune(gdp_ctx* c, int iters, void* stream, int* best_variant, int* best_order, float* best_ms) try {
+    GDP_BUILDS_PYRAMID(c);
     // Times every build-kernel variant x tile order x store mode on the context's current input
     // (HIP events on `stream`, median of 3 repeats of `iters` launches) and keeps the fastest.
     // Store modes (zero window, store pace): (0, off), (0, 1), (1, off), (1, 0) — the pairs that won
@@ -2727,11 +2813,14 @@ int gdp_get_tuning(const gdp_ctx* c, int key, int* value) try {
         case GDP_TUNE_STAGE_KB: *value = (int)(c->stage_half_floats / 256); return GDP_OK;
         case GDP_TUNE_STAGE_THREADS: *value = c->stage_threads; return GDP_OK;
         case GDP_TUNE_PYRAMID_CHUNK_KB: *value = c->pyr_chunk_kb; return GDP_OK;
+        case GDP_TUNE_KEEP_ZEROS: *value = c->keep_zeros; return GDP_OK;
+        case GDP_TUNE_ZEROS_CLEAN: *value = c->zeros_clean ? 1 : 0; return GDP_OK;
         default: return GDP_ERR_ARG;
     }
 } GDP_ABI_CATCH(c)
 
 int gdp_set_tuning(gdp_ctx* c, int key, int value) try {
+    GDP_READS_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
     switch (key) {
         case GDP_TUNE_NONTEMPORAL:
@@ -2795,6 +2884,12 @@ int gdp_set_tuning(gdp_ctx* c, int key, int value) try {
             }
             return rc;
         }
+        case GDP_TUNE_KEEP_ZEROS:
+            if (value != 0 && value != 1) return c->status(GDP_ERR_ARG, "keep zeros must be 0 or 1");
+            c->keep_zeros = value;  // a launch-time decision (a kernel argument): no geometry upload, no drain
+            return GDP_OK;
+        case GDP_TUNE_ZEROS_CLEAN:
+            return c->status(GDP_ERR_ARG, "GDP_TUNE_ZEROS_CLEAN is read-only (gdp_pyramid_written clears it)");
         case GDP_TUNE_CONV_ORDER:
             if (value < 0 || value > 7) return c->status(GDP_ERR_ARG, "conv order must be 0..7");
             c->conv_order = value;
@@ -2834,14 +2929,17 @@ int gdp_set_tuning(gdp_ctx* c, int key, int value) try {
 } GDP_ABI_CATCH(c)
 
 int gdp_time_builds(gdp_ctx* c, int iters, void* stream, float* total_ms) try {
+    GDP_BUILDS_PYRAMID(c);
     if (!c || iters <= 0 || !total_ms) return c ? c->status(GDP_ERR_ARG, "gdp_time_builds: bad argument") : GDP_ERR_ARG;
     GDP_HIP(c, hipSetDevice(c->device));
     hipStream_t st = c->pick(stream);
     hipEvent_t e0, e1;
     GDP_HIP(c, hipEventCreate(&e0));
     GDP_HIP(c, hipEventCreate(&e1));
-    int rc = GDP_OK;
-    if (hipEventRecord(e0, st) != hipSuccess) rc = c->status(GDP_ERR_HIP, "hipEventRecord");
+    // one untimed build first: every timed launch then runs in the same (clean, GDP_TUNE_KEEP_ZEROS)
+    // state, whatever the caller did to the pyramid before
+    int rc = launch_build(c, st);
+    if (rc == GDP_OK && hipEventRecord(e0, st) != hipSuccess) rc = c->status(GDP_ERR_HIP, "hipEventRecord");
     for (int i = 0; i < iters && rc == GDP_OK; ++i) rc = launch_build(c, st);
     if (rc == GDP_OK && hipEventRecord(e1, st) != hipSuccess) rc = c->status(GDP_ERR_HIP, "hipEventRecord");
     if (rc == GDP_OK && hipEventSynchronize(e1) != hipSuccess) rc = c->status(GDP_ERR_HIP, "hipEventSynchronize");

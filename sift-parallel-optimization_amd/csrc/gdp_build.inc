@@ -8,10 +8,12 @@
 // (GaussDePyramid-AVX512xOpenMP.h:240-364): only scales 0..S-1 are windowed (:242-318, row pass
 // then column pass, so the same (x * fc_s) * fr_s), DoG only for s < S-1 (:337-357), and levels
 // S..S+2 keep GaussPyInit's value x.
+// `keep` != 0 (never for SUB, whose levels S..S+2 hold x): the context's pyramid already holds the
+// input-independent +0 of every DoG level outside the windows' support, so those stores are skipped.
 template <int LT, bool NT, bool SUB = false>
 __device__ __forceinline__ void build_group(const Geom* __restrict__ g, const void* __restrict__ in,
-                                            float* __restrict__ out, const float* __restrict__ taps, int b,
-                                            int o, const OctGeom& og, int Rl, int C) {
+                                            float* __restrict__ out, const float* __restrict__ taps, int keep,
+                                            int b, int o, const OctGeom& og, int Rl, int C) {
     const int L = LT > 0 ? LT : g->L;
     const int n = min(4, og.cols - C);
     const int Rg = og.row0 + Rl;
@@ -43,6 +45,19 @@ __device__ __forceinline__ void build_group(const Geom* __restrict__ g, const vo
             st_f4<NT>(dst + (L - 1) * og.lev_stride, gp);
         else
             st_part(dst + (L - 1) * og.lev_stride, gp, n, false);
+        return;
+    }
+    if (keep && outside_support(og, Rg, C, n)) {
+        // Clean pyramid (gdp_ctx::zeros_clean; `keep` is a wave-uniform kernel argument): outside the
+        // TRUE support (OctGeom::sp_*, whatever GDP_TUNE_ZERO_WINDOW says) the S+2 DoG levels are +0
+        // for any input, and an earlier build of this context already stored exactly that — nothing
+        // has written the pyramid since.  Only level L-1 = copysign(0, x) depends on the image: one
+        // load, one store, no window loads and no pace wait.
+        const f4 last = __builtin_bit_cast(f4, __builtin_bit_cast(i4, x) & (int)0x80000000u);
+        if (full)
+            st_f4<NT>(dst + (L - 1) * og.lev_stride, last);
+        else
+            st_part(dst + (L - 1) * og.lev_stride, last, n, false);
         return;
     }
     if (zero_support(og, Rg, C, n)) {
@@ -97,7 +112,8 @@ __device__ __forceinline__ void build_group(const Geom* __restrict__ g, const vo
 // 2 v16 0.0861 vs 0.0857, config 4 v16 5.38 vs 5.40; profiles/ab_tail_c*_r03z.log.)
 template <int LT, bool NT, int BLK, bool SUB>
 __device__ __forceinline__ void build_tail_unit(const Geom* __restrict__ g, const void* __restrict__ in,
-                                                float* __restrict__ out, const float* __restrict__ taps, unsigned tu) {
+                                                float* __restrict__ out, const float* __restrict__ taps, int keep,
+                                                unsigned tu) {
     const int F = g->F;
     for (int q = threadIdx.x; q < kTailGroups; q += BLK) {
         const unsigned t = tu * kTailGroups + q;
@@ -111,7 +127,7 @@ __device__ __forceinline__ void build_tail_unit(const Geom* __restrict__ g, cons
         const int k = (int)(rem - og.grp_begin);
         const int Rl = k / og.gpr;
         const int C = 4 * (k - Rl * og.gpr);
-        build_group<LT, NT, SUB>(g, in, out, taps, (int)b, o, og, Rl, C);
+        build_group<LT, NT, SUB>(g, in, out, taps, keep, (int)b, o, og, Rl, C);
     }
 }
 
@@ -127,7 +143,7 @@ __device__ __forceinline__ void build_tail_unit(const Geom* __restrict__ g, cons
 // round 5 with the variants that used them — DESIGN_HISTORY §4.)
 template <int LT, bool NT, int BLK, int TC, int PATH, int TR, bool SUB>
 __device__ __forceinline__ void build_body(const Geom* __restrict__ g, const void* __restrict__ in,
-                                           float* __restrict__ out, const float* __restrict__ taps) {
+                                           float* __restrict__ out, const float* __restrict__ taps, int keep) {
     const unsigned tiles_total = g->tiles_total;
     const unsigned units = tiles_total + g->tail_units;
     const int F = g->F;
@@ -165,7 +181,7 @@ __device__ __forceinline__ void build_body(const Geom* __restrict__ g, const voi
                         if (q >= (unsigned)og.span || lo + q >= total) break;
                         const int Rl = (int)fast_div(lo + q, og.gpr_magic, og.gpr_shift);
                         const int C = 4 * (int)(lo + q - (unsigned)Rl * (unsigned)og.gpr);
-                        build_group<LT, NT, SUB>(g, in, out, taps, (int)b, 0, og, Rl, C);
+                        build_group<LT, NT, SUB>(g, in, out, taps, keep, (int)b, 0, og, Rl, C);
                     }
                 }
                 if constexpr (PATH == 4) {
@@ -181,7 +197,7 @@ __device__ __forceinline__ void build_body(const Geom* __restrict__ g, const voi
                         if (grp >= (unsigned)og.rows * (unsigned)og.gpr) continue;
                         const int Rl = (int)fast_div(grp, og.gpr_magic, og.gpr_shift);
                         const int C = 4 * (int)(grp - (unsigned)Rl * (unsigned)og.gpr);
-                        build_group<LT, NT, SUB>(g, in, out, taps, (int)b, o, og, Rl, C);
+                        build_group<LT, NT, SUB>(g, in, out, taps, keep, (int)b, o, og, Rl, C);
                     }
                 } else {
                     // PATH 5, source-aligned: octave o's groups whose first input pixel (r << o,
@@ -212,7 +228,7 @@ __device__ __forceinline__ void build_body(const Geom* __restrict__ g, const voi
                             const unsigned grp = lo + (idx - base);
                             const int Rl = (int)fast_div(grp, og.gpr_magic, og.gpr_shift);
                             const int C = 4 * (int)(grp - (unsigned)Rl * (unsigned)og.gpr);
-                            build_group<LT, NT, SUB>(g, in, out, taps, (int)b, o, og, Rl, C);
+                            build_group<LT, NT, SUB>(g, in, out, taps, keep, (int)b, o, og, Rl, C);
                         }
                         base += cnt;
                     }
@@ -249,7 +265,7 @@ __device__ __forceinline__ void build_body(const Geom* __restrict__ g, const voi
                         if (q >= TR * gpr_t) break;
                         const int r = q / gpr_t, cg = q - r * gpr_t;
                         const int Rl = in_r0 + r, C = in_c0 + 4 * cg;
-                        if (Rl < og.rows && C < og.cols) build_group<LT, NT, SUB>(g, in, out, taps, (int)b, 0, og, Rl, C);
+                        if (Rl < og.rows && C < og.cols) build_group<LT, NT, SUB>(g, in, out, taps, keep, (int)b, 0, og, Rl, C);
                     }
                 }
                 for (int q = (int)threadIdx.x; q < kRest; q += BLK) {
@@ -267,7 +283,7 @@ __device__ __forceinline__ void build_body(const Geom* __restrict__ g, const voi
                     const int gpr_t = (TC / 4) >> o;
                     const int r = qq / gpr_t, cg = qq - r * gpr_t;
                     const int Rl = (in_r0 >> o) + r, C = (in_c0 >> o) + 4 * cg;
-                    if (Rl < og.rows && C < og.cols) build_group<LT, NT, SUB>(g, in, out, taps, (int)b, o, og, Rl, C);
+                    if (Rl < og.rows && C < og.cols) build_group<LT, NT, SUB>(g, in, out, taps, keep, (int)b, o, og, Rl, C);
                 }
                 continue;
             }
@@ -287,11 +303,11 @@ __device__ __forceinline__ void build_body(const Geom* __restrict__ g, const voi
                     // in_r0 + (r << o) maps to local output row (in_r0 >> o) + r.
                     const int Rl = (in_r0 >> o) + r;
                     const int C = (in_c0 >> o) + 4 * cg;
-                    if (Rl < og.rows && C < og.cols) build_group<LT, NT, SUB>(g, in, out, taps, (int)b, o, og, Rl, C);
+                    if (Rl < og.rows && C < og.cols) build_group<LT, NT, SUB>(g, in, out, taps, keep, (int)b, o, og, Rl, C);
                 }
             }
         } else {
-            build_tail_unit<LT, NT, BLK, SUB>(g, in, out, taps, u - tiles_total);
+            build_tail_unit<LT, NT, BLK, SUB>(g, in, out, taps, keep, u - tiles_total);
         }
     }
 }
@@ -318,11 +334,11 @@ __device__ __forceinline__ void trace_wave(unsigned long long t_in, int waves_pe
 
 template <int LT, bool NT, int BLK, int TC, int PATH, int TR, bool SUB = false>
 __global__ void __launch_bounds__(BLK) k_build(const Geom* __restrict__ g, const void* __restrict__ in,
-                                               float* __restrict__ out, const float* __restrict__ taps) {
+                                               float* __restrict__ out, const float* __restrict__ taps, int keep) {
 #ifdef GDP_TRACE_BLOCKS
     const unsigned long long t_in = __builtin_amdgcn_s_memrealtime();
 #endif
-    build_body<LT, NT, BLK, TC, PATH, TR, SUB>(g, in, out, taps);
+    build_body<LT, NT, BLK, TC, PATH, TR, SUB>(g, in, out, taps, keep);
 #ifdef GDP_TRACE_BLOCKS
     trace_wave(t_in, BLK / 64);
 #endif
@@ -337,8 +353,8 @@ __global__ void __launch_bounds__(BLK) k_build(const Geom* __restrict__ g, const
 // numbers): GDP_TUNE_VARIANT refuses their ids.
 struct BuildVariant {
     int id, block, tile_cols, tile_rows;
-    void (*k[2][2])(const Geom*, const void*, float*, const float*); // [LT==5][NT]
-    void (*ksub[2][2])(const Geom*, const void*, float*, const float*); // [LT==5][NT]
+    void (*k[2][2])(const Geom*, const void*, float*, const float*, int); // [LT==5][NT]
+    void (*ksub[2][2])(const Geom*, const void*, float*, const float*, int); // [LT==5][NT]
 };
 #define GDP_VARIANT(ID, BLK, TC, REG, TR)                                                         \
     BuildVariant {                                                                                \

@@ -323,6 +323,8 @@ int gdp_comm_gather_bands(gdp_comm* c, gdp_ctx* band, int band_image, gdp_ctx* f
                 return fail(c, GDP_ERR_ARG, "band context rows differ from gdp_band_rows' band of this rank");
         }
     }
+    // the receives and the copies below write `full`'s pyramid through gdp_device_level's pointer
+    if (full) gdp_pyramid_written(full, full_image);
     int rc = group_start(c, st);
     if (rc != GDP_OK) return rc;
     for (const gdp_transfer& t : plan) {
@@ -373,6 +375,7 @@ int gdp_comm_collect_scales(gdp_comm* c, gdp_ctx* ctx, int image, void* stream) 
     if (plan.empty()) return GDP_OK;  // ranks > S+3 take no part (GaussDePyramid-MPI.h:269-335)
     GDP_HIPC(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)gdp_stream(ctx);
+    gdp_pyramid_written(ctx, image);  // the receives write ctx's levels through gdp_device_level's pointer
     int rc = group_start(c, st);
     if (rc != GDP_OK) return rc;
     for (const gdp_scale_transfer& t : plan) {

@@ -43,13 +43,23 @@ struct OctGeom {
     // The build's int32 inputs never overflow (|x| < 2^31, taps < 2), so it uses nz_r*; the in-place
     // passes use these, which cover the whole octave when some column tap exceeds 1 (ADVICE r3).
     int nzi_r0, nzi_r1;
-    int span;             // contiguous-span build variants (PATH 4): groups of this octave per unit
+    // The TRUE window support, whatever the knob says (set once at context creation, both window
+    // centres): the build's `keep` test (outside_support).  On a clean pyramid the DoG levels of a
+    // group outside these ranges already hold their +0, so the build does not store them again.
+    int sp_r0, sp_r1, sp_c0, sp_c1;
+    int span;            // contiguous-span build variants (PATH 4): groups of this octave per unit
 };
 
 // Group (global row Rg, columns C..C+n-1) outside the support of every window of its octave
 // (GDP_TUNE_ZERO_WINDOW; always false with the knob off, the ranges then cover the octave).
 __device__ __forceinline__ bool zero_support(const OctGeom& og, int Rg, int C, int n) {
     return Rg < og.nz_r0 || Rg >= og.nz_r1 || C + n <= og.nz_c0 || C >= og.nz_c1;
+}
+
+// Group outside the true support (OctGeom::sp_*, independent of GDP_TUNE_ZERO_WINDOW): its DoG
+// levels are +0 for any input — the stores a build skips on a clean pyramid (k_build's `keep`).
+__device__ __forceinline__ bool outside_support(const OctGeom& og, int Rg, int C, int n) {
+    return Rg < og.sp_r0 || Rg >= og.sp_r1 || C + n <= og.sp_c0 || C >= og.sp_c1;
 }
 
 // The same for the in-place window passes on caller-written floats (OctGeom::nzi_*): a column

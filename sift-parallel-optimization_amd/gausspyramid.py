@@ -289,7 +289,8 @@ class PyramidContext:
 
     _TUNING = ("nontemporal", "blocks_per_cu", "grid", "variant", "tile_order", "inplace_sub", "window_sub",
                "conv_kernel", "conv_rows", "conv_order", "build_lds", "stage_kb", "stage_threads", "conv_waves", "zero_window",
-               "store_pace", "conv_pace", "inplace_pace", "pyramid_chunk_kb")  # the last one read-only
+               "store_pace", "conv_pace", "inplace_pace", "keep_zeros",
+               "pyramid_chunk_kb", "zeros_clean")  # the last two read-only
 
     @staticmethod
     def _tuning_key(name):
@@ -300,7 +301,7 @@ class PyramidContext:
     def set_tuning(self, nontemporal=None, blocks_per_cu=None, grid=None, variant=None, tile_order=None,
                    inplace_sub=None, window_sub=None, conv_kernel=None, conv_rows=None, conv_order=None,
                    build_lds=None, stage_kb=None, stage_threads=None, conv_waves=None, zero_window=None,
-                   store_pace=None, conv_pace=None, inplace_pace=None):
+                   store_pace=None, conv_pace=None, inplace_pace=None, keep_zeros=None):
         """Performance knobs of the kernels (outputs are bit-identical for every setting; the
         conv_* knobs select the convolution extension's kernel: 0 register sweep, 1 LDS tiles,
         2 block tiles, and the sweep's rows per wave strip (16 / 32) or the block tiles' rows per
@@ -309,12 +310,15 @@ class PyramidContext:
         size the double-buffered pinned staging of the row-pointer downloads; zero_window = 1 lets the
         build store the input-independent levels of pixels outside every window's support without
         waiting for their input; store_pace / conv_pace / inplace_pace pace the stores of the
-        builds / the convolution block tiles / the in-place re-entry, each its own field)."""
+        builds / the convolution block tiles / the in-place re-entry, each its own field;
+        keep_zeros = 0 makes every build store every byte, instead of leaving the input-independent
+        zeros outside the windows' support that the previous build of this context already stored —
+        tuning()["zeros_clean"] tells whether the next build may leave them)."""
         vals = dict(nontemporal=nontemporal, blocks_per_cu=blocks_per_cu, grid=grid, variant=variant,
                     tile_order=tile_order, inplace_sub=inplace_sub, window_sub=window_sub, conv_kernel=conv_kernel,
                     conv_rows=conv_rows, conv_order=conv_order, build_lds=build_lds, stage_kb=stage_kb,
                     stage_threads=stage_threads, conv_waves=conv_waves, zero_window=zero_window,
-                    store_pace=store_pace, conv_pace=conv_pace, inplace_pace=inplace_pace)
+                    store_pace=store_pace, conv_pace=conv_pace, inplace_pace=inplace_pace, keep_zeros=keep_zeros)
         for name, val in vals.items():
             if val is not None:
                 check(lib().gdp_set_tuning(self._ctx, self._tuning_key(name), int(val)), self._ctx)
@@ -446,7 +450,14 @@ class PyramidContext:
         return recs.value, count.value
 
     def device_level_ptr(self, b, o, s):
+        """Device address of level (o, s) of image b.  Read-only: after writing through it, call
+        pyramid_written() before the next build."""
         return lib().gdp_device_level(self._ctx, int(b), int(o), int(s))
+
+    def pyramid_written(self, b=-1):
+        """Image b's pyramid (b < 0: every image's) was written by something other than libgdp: the
+        next build stores every byte again (gdp_pyramid_written)."""
+        check(lib().gdp_pyramid_written(self._ctx, int(b)), self._ctx)
 
     def taps(self, axis, o, s):
         """Window the device holds: axis 0 = column taps (from W), 1 = row taps (from H)."""

@@ -39,7 +39,9 @@ def run(args):
     ctxs = [pkg.PyramidContext(H, W, S=2, octaves=O, batch=B, row_begin=r0, row_end=r1) for _ in range(rotate)]
     for c in ctxs:
         c.fill_synthetic(bench.SEED, 0)
-        c.set_tuning(zero_window=args.zero_window)
+        # the classic records count a build that stores every byte (keep_zeros = 0, the first build
+        # of a context); --keep-zeros 1 counts the steady state (every set built once before)
+        c.set_tuning(zero_window=args.zero_window, keep_zeros=args.keep_zeros)
         if args.op == "subset":  # bench.py --op subset's contexts
             c.set_window_centre("intlen")
         c.sync()
@@ -49,22 +51,23 @@ def run(args):
         if only is None or v in only:
             order += [(v, 0), (v, 1)]
     manifest = []
+    warm = max(args.warm, rotate) if args.keep_zeros else args.warm  # steady state: every set clean first
     for v, t in order:
         for c in ctxs:
             c.set_tuning(variant=v, tile_order=t)
         n = 0
-        for i in range(args.warm + args.reps):  # consecutive launches cycle through the cold sets
+        for i in range(warm + args.reps):  # consecutive launches cycle through the cold sets
             (ctxs[i % rotate].build_subset if args.op == "subset" else ctxs[i % rotate].build)()
             n += 1
         for c in ctxs:
             c.sync()
-        manifest.append({"variant": v, "tile_order": t, "dispatches": n, "warm": args.warm})
+        manifest.append({"variant": v, "tile_order": t, "dispatches": n, "warm": warm})
     chunk_kb = ctxs[0].tuning().get("pyramid_chunk_kb", 0)
     for c in ctxs:
         c.close()
     with open(args.manifest, "w") as f:
         json.dump({"config": args.config, "op": args.op, "rotate": rotate, "zero_window": args.zero_window,
-                   "band_of": args.band_of, "band": [r0, r1], "instances": manifest,
+                   "keep_zeros": args.keep_zeros, "band_of": args.band_of, "band": [r0, r1], "instances": manifest,
                    "image_stride_mb": int(os.environ["GDP_IMAGE_STRIDE_MB"]) if os.environ.get("GDP_IMAGE_STRIDE_MB")
                    else None, "pyramid_chunk_kb": chunk_kb}, f)
 
@@ -119,7 +122,11 @@ def summarise(args):
         read_b = 2 * statistics.median(v for _, v, _ in fs) * 1024
         write_b = statistics.median(v for _, v, _ in ws) * 1024
         rec = {"config": man["config"], "round": args.round, "kernel": fs[0][2], "variant": m["variant"],
-               "tile_order": m["tile_order"], "input_format": "i32", "op": man.get("op", "build"),
+               "tile_order": m["tile_order"], "input_format": "i32",
+               # a steady-state (kept) build moves fewer bytes than the algorithmic count: its own op,
+               # so bench.py's roofline.traffic never takes it for the full build's record
+               "op": "build_kept" if man.get("keep_zeros") else man.get("op", "build"),
+               "keep_zeros": man.get("keep_zeros", 0),
                "zero_window": man.get("zero_window", 0),
                **({"band_of": band_of, "band_rows": [r0, r1]} if band_of else {}),
                **({"image_stride_mb": man["image_stride_mb"]} if man.get("image_stride_mb") else {}),
@@ -134,7 +141,7 @@ def summarise(args):
                "correction": "read = 2 x FETCH_SIZE KiB (gfx950 half-count of wide streaming reads); write = WRITE_SIZE KiB"}
         tag = man["config"] + (f"b{band_of}" if band_of else "") + ("_subset" if man.get("op") == "subset" else "")
         zw = ("z1" if man.get("zero_window", 0) else "") + (f"s{man['image_stride_mb']}" if man.get("image_stride_mb") else "") \
-            + (f"k{man['pyramid_chunk_kb']}" if man.get("pyramid_chunk_kb") else "")
+            + (f"k{man['pyramid_chunk_kb']}" if man.get("pyramid_chunk_kb") else "") + ("kept" if man.get("keep_zeros") else "")
         out = os.path.join(REPO, "profiles", f"pmc_{tag}_v{m['variant']}o{m['tile_order']}{zw}_{args.round}.json")
         if os.path.exists(out) and not args.overwrite:
             print("keep", out)
@@ -155,6 +162,9 @@ def main():
                     help="subset: the GenerateDoG_nomp_dynamic build (bench.py --op subset)")
     ap.add_argument("--zero-window", type=int, default=0, choices=[0, 1],
                     help="GDP_TUNE_ZERO_WINDOW of every instance (records pmc_<cfg>_v<V>o<T>z1_*.json)")
+    ap.add_argument("--keep-zeros", type=int, default=0, choices=[0, 1],
+                    help="GDP_TUNE_KEEP_ZEROS: 0 (default) every counted build stores every byte; 1 the steady state "
+                         "of a rebuilt context (records pmc_<cfg>_v<V>o<T>...kept_*.json, op build_kept)")
     ap.add_argument("--variants", default=None, help="comma-separated variant numbers to profile (default: all)")
     ap.add_argument("--band-of", type=int, default=None,
                     help="row-band config: profile rank 0's band of N ranks (bench.py --gpus N --config c5's "
