@@ -483,10 +483,19 @@ enum {
                                    they are +0 for any input and already there; level S+2 and the
                                    support are stored as ever.  The same bits either way; 0 = every
                                    build stores every byte.  A launch-time flag: no drain */
-    GDP_TUNE_ZEROS_CLEAN = 22   /* read-only: 1 while the next gdp_build may skip those stores (set
+    GDP_TUNE_ZEROS_CLEAN = 22,  /* read-only: 1 while the next gdp_build may skip those stores (set
                                    by a gdp_build into the context-owned pyramid, cleared by every
                                    call that writes, moves or rebinds pyramid memory and by
                                    gdp_pyramid_written) */
+    GDP_TUNE_KEEP_KERNEL = 23   /* the kernel of a gdp_build that skips those stores (the steady
+                                   state): 0 = the build kernel's own keep path; 1, 2 = the
+                                   steady-state kernel k_keep — one pass over the input on
+                                   16 x 256 tiles, level S+2 of every fused octave stored from the
+                                   registers that hold the octave-0 pixels — with 4 or 2 rows per
+                                   wave (default by pixels per launch: 0 under 8 Mpix, 2 up to 64 Mpix,
+                                   1 above).  Taken when the width is a multiple of 4 and the input
+                                   allows one vector load per 4 pixels; any other context runs 0.
+                                   The same bits either way.  A launch-time flag: no drain */
 };
 int gdp_set_tuning(gdp_ctx* ctx, int key, int value);
 /* The build-kernel variant ids this library holds (GDP_TUNE_VARIANT values): writes up to

@@ -32,6 +32,7 @@ GDP_TUNE_INPLACE_PACE = 19
 GDP_TUNE_PYRAMID_CHUNK_KB = 20
 GDP_TUNE_KEEP_ZEROS = 21
 GDP_TUNE_ZEROS_CLEAN = 22
+GDP_TUNE_KEEP_KERNEL = 23
 
 
 class GdpError(RuntimeError):

@@ -50,6 +50,7 @@ namespace {
 
 #include "gdp_geom.inc"
 #include "gdp_build.inc"
+#include "gdp_keep.inc"
 #include "gdp_inplace.inc"
 #include "gdp_conv.inc"
 #include "gdp_extrema.inc"
@@ -150,6 +151,8 @@ struct gdp_ctx {
     // stream (the build must be ordered after the writer for its own stores to survive).
     bool zeros_clean = false;
     int keep_zeros = 1;           // GDP_TUNE_KEEP_ZEROS: 0 = every build stores every byte
+    int keep_kernel = 1;          // GDP_TUNE_KEEP_KERNEL: 0 = a kept build runs k_build's keep path, >= 1 = k_keep
+                                  // (kKeepKernels) where the context is eligible (launch_build); default by size
     long long img_floats = 0;     // one image's dense extent (pyr_stride may be larger: GDP_IMAGE_STRIDE_MB)
     // GDP_SPREAD_VMM: the pyramid as one reserved address range with separately created physical
     // chunks mapped into it (alloc_spread); each entry: handle, byte offset, bytes
@@ -296,6 +299,18 @@ int launch_build(gdp_ctx* c, hipStream_t st, bool subset = false) {
     // default: one unit per block; GDP_TUNE_GRID / GDP_TUNE_BLOCKS_PER_CU cap it (persistent loop)
     const long long cap = c->grid_override > 0 ? c->grid_override : (c->persistent ? c->blocks_max : units);
     const int grid = (int)std::min<long long>(units, cap);
+    if (keep && c->keep_kernel > 0 && g.W % 4 == 0 && g.vec_in) {
+        // The steady-state build's own kernel (gdp_keep.inc): whole 4-pixel groups and aligned vector
+        // loads everywhere; any other context keeps k_build's keep path below.  Its units are the
+        // Geom's kp_* fields, whatever variant is selected; a launch-time choice like `keep` itself.
+        const long long kunits = (long long)g.kp_tiles_total + g.kp_tail_units;
+        const KeepKernel& kk = kKeepKernels[c->keep_kernel - 1];
+        hipLaunchKernelGGL(kk.k[c->nontemporal ? 1 : 0], dim3((unsigned)std::min<long long>(kunits, cap)), dim3(kk.block), 0,
+                           st, c->d_geom, c->d_in, c->d_out, c->d_taps);
+        GDP_HIP(c, hipGetLastError());
+        c->zeros_clean = true;  // keep != 0: a full build into the context's own pyramid
+        return GDP_OK;
+    }
     const BuildVariant& v = kVariants[variant_index(c->variant)];
     auto kern = (subset ? v.ksub : v.k)[g.L == 5][c->nontemporal ? 1 : 0];
     hipLaunchKernelGGL(kern, dim3(grid), dim3(v.block), (unsigned)c->build_lds, st, c->d_geom, c->d_in, c->d_out,
@@ -442,6 +457,13 @@ void set_window_support(gdp_ctx* c, bool on) {
         OctGeom& og = g.oct[o];
         const auto& r = c->support[(size_t)o];
         og.sp_r0 = r[0], og.sp_r1 = r[1], og.sp_c0 = r[2], og.sp_c1 = r[3];  // the keep test: knob-independent
+        if (o == g.kp_F - 1) {
+            // k_keep's tile order starts at the first tile row that meets the support of the coarsest
+            // fused octave (the tallest in input rows: about 29 << o rows either side of the centre)
+            const int tiles_r = std::max(1, (g.in_rows + kTileRows - 1) / kTileRows);
+            const long long first = ((long long)r[0] << o) - g.in_row0;
+            g.kp_row_start = (int)std::min<long long>(tiles_r - 1, std::max<long long>(0, first / kTileRows));
+        }
         if (on) {
             og.nz_r0 = r[0], og.nz_r1 = r[1], og.nz_c0 = r[2], og.nz_c1 = r[3];
             og.nzi_r0 = r[4] ? r[0] : 0;
@@ -932,6 +954,17 @@ int gdp_create_band(gdp_ctx** out, int H, int W, int S, int O, int batch, int ro
     // single images (4096^2 0.148 vs 0.152 ms for 256 threads, 16384^2 2.37 vs 2.49;
     // profiles/ab_sub_c*_r03m.log), 256-thread blocks on small batches, 1024-thread above
     c->inplace_sub = batch == 1 ? 16 : (long long)(row_end - row_begin) * W * batch <= (32ll << 20) ? 4 : 1;
+    // Steady-state build (k_keep, GDP_TUNE_KEEP_KERNEL), by pixels per launch — measured on the rotated cold
+    // sets bench.py times (profiles/keep_kernel_shapes_r08.json; ms for kernel 0 / 1 / 2):
+    //   under 8 Mpix the launch is all ramp and drain and k_build's 16-wave blocks win: 2048^2 0.0145 / 0.0219 /
+    //   0.0156 -> 0;
+    //   up to 64 Mpix 8-wave blocks, 2 rows per wave — more, shorter waves: 4096^2 0.0421 / 0.0381 / 0.0294,
+    //   8 x 1080x1920 0.0435 / 0.0446 / 0.0410, 8192 x 4096 0.0799 / 0.0596 / 0.0540, 4 x 4096^2 0.1576 / 0.1111 /
+    //   0.1037 -> 2;
+    //   above, 4-wave blocks with 4 KiB of loads in flight per wave: 64 x 1080x1920 0.3225 / 0.2520 / 0.2725,
+    //   64 x 4096^2 2.450 / 1.582 / 1.601, 16384^2 0.598 / 0.393 / 0.391 -> 1.
+    const long long kp_px = (long long)(row_end - row_begin) * W * batch;
+    c->keep_kernel = kp_px < (1ll << 23) ? 0 : kp_px <= (1ll << 26) ? 2 : 1;
     // Convolution extension default: block tiles (16 waves) in block order 5 (below; octave-o block
     // rows right after the octave-0 rows that hold their input rows, XCD-chunked) — the fastest form
     // on every config (tools/conv_ab.sh, cold buffers: 4096^2 0.111 ms vs 0.119 for the sweep,
@@ -1050,6 +1083,15 @@ int gdp_create_band(gdp_ctx** out, int H, int W, int S, int O, int batch, int ro
     }
     g.tail_groups_per_img = (unsigned)tail_per_img;
     g.tail_units = (unsigned)tail_units;
+    // k_keep's units: 16 x 256 tiles and the tail of the octaves >= min(O, kFused), as computed just
+    // above — retile() replaces F and the tail counts with the selected variant's, never these
+    g.kp_F = g.F;
+    g.kp_tiles_c = (W + kTileCols - 1) / kTileCols;
+    g.kp_tiles_per_img = (unsigned)((g.in_rows + kTileRows - 1) / kTileRows) * (unsigned)g.kp_tiles_c;
+    g.kp_tiles_total = g.kp_tiles_per_img * (unsigned)batch;  // <= min_tiles, checked above
+    g.kp_tail_groups_per_img = (unsigned)tail_per_img;
+    g.kp_tail_units = (unsigned)tail_units;
+    g.kp_row_start = g.kp_pad_ = 0;  // set with the support (set_window_support)
     // Tile order default: linear.  (With v0 a single >= 64 Mpix image streamed 7-8 % faster in
     // the XCD-chunked order; with the default v15 the linear order is the faster one on 16384^2,
     // 1.344 vs 1.375 ms, and batches differ box to box — gdp_autotune measures both.)
@@ -2815,6 +2857,7 @@ int gdp_get_tuning(const gdp_ctx* c, int key, int* value) try {
         case GDP_TUNE_PYRAMID_CHUNK_KB: *value = c->pyr_chunk_kb; return GDP_OK;
         case GDP_TUNE_KEEP_ZEROS: *value = c->keep_zeros; return GDP_OK;
         case GDP_TUNE_ZEROS_CLEAN: *value = c->zeros_clean ? 1 : 0; return GDP_OK;
+        case GDP_TUNE_KEEP_KERNEL: *value = c->keep_kernel; return GDP_OK;
         default: return GDP_ERR_ARG;
     }
 } GDP_ABI_CATCH(c)
@@ -2887,6 +2930,11 @@ int gdp_set_tuning(gdp_ctx* c, int key, int value) try {
         case GDP_TUNE_KEEP_ZEROS:
             if (value != 0 && value != 1) return c->status(GDP_ERR_ARG, "keep zeros must be 0 or 1");
             c->keep_zeros = value;  // a launch-time decision (a kernel argument): no geometry upload, no drain
+            return GDP_OK;
+        case GDP_TUNE_KEEP_KERNEL:
+            if (value < 0 || value > kNumKeepKernels)
+                return c->status(GDP_ERR_ARG, "keep kernel must be 0 (k_build's keep path) or 1..%d (k_keep)", kNumKeepKernels);
+            c->keep_kernel = value;  // a launch-time decision like GDP_TUNE_KEEP_ZEROS: no geometry upload, no drain
             return GDP_OK;
         case GDP_TUNE_ZEROS_CLEAN:
             return c->status(GDP_ERR_ARG, "GDP_TUNE_ZEROS_CLEAN is read-only (gdp_pyramid_written clears it)");

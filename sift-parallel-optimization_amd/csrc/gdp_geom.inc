@@ -115,6 +115,12 @@ struct Geom {
     unsigned tail_groups_per_img, tail_units;  // octaves >= F, 256 groups per unit
     int span_rest;        // contiguous-span variants: sum of OctGeom::span over octaves >= 1
     int pad_span_;
+    // k_keep (gdp_keep.inc, GDP_TUNE_KEEP_KERNEL): its own kTileRows x kTileCols tile grid and tail
+    // split (octaves >= kp_F), set once at context creation — independent of the selected build variant
+    int kp_F, kp_tiles_c;
+    int kp_row_start, kp_pad_; // first tile row that meets some fused octave's support: k_keep's tile order starts there
+    unsigned kp_tiles_per_img, kp_tiles_total;
+    unsigned kp_tail_groups_per_img, kp_tail_units;
     OctGeom oct[kMaxOct];
     unsigned lv_blk[kMaxOct + 1]; // prefix over octaves of ceil(rows*gpr / kLevBlock) per image
     unsigned lx_blk[kMaxOct + 1]; // prefix over octaves of ceil(rows*gpr / 64) per image (k_levels_x)

@@ -41,7 +41,8 @@ def run(args):
         c.fill_synthetic(bench.SEED, 0)
         # the classic records count a build that stores every byte (keep_zeros = 0, the first build
         # of a context); --keep-zeros 1 counts the steady state (every set built once before)
-        c.set_tuning(zero_window=args.zero_window, keep_zeros=args.keep_zeros)
+        # --keep-kernel: the kernel of those steady-state builds (GDP_TUNE_KEEP_KERNEL; default: the library's)
+        c.set_tuning(zero_window=args.zero_window, keep_zeros=args.keep_zeros, keep_kernel=args.keep_kernel)
         if args.op == "subset":  # bench.py --op subset's contexts
             c.set_window_centre("intlen")
         c.sync()
@@ -63,11 +64,12 @@ def run(args):
             c.sync()
         manifest.append({"variant": v, "tile_order": t, "dispatches": n, "warm": warm})
     chunk_kb = ctxs[0].tuning().get("pyramid_chunk_kb", 0)
+    keep_kernel = ctxs[0].tuning()["keep_kernel"] if args.keep_zeros else 0
     for c in ctxs:
         c.close()
     with open(args.manifest, "w") as f:
         json.dump({"config": args.config, "op": args.op, "rotate": rotate, "zero_window": args.zero_window,
-                   "keep_zeros": args.keep_zeros, "band_of": args.band_of, "band": [r0, r1], "instances": manifest,
+                   "keep_zeros": args.keep_zeros, "keep_kernel": keep_kernel, "band_of": args.band_of, "band": [r0, r1], "instances": manifest,
                    "image_stride_mb": int(os.environ["GDP_IMAGE_STRIDE_MB"]) if os.environ.get("GDP_IMAGE_STRIDE_MB")
                    else None, "pyramid_chunk_kb": chunk_kb}, f)
 
@@ -97,7 +99,8 @@ def per_dispatch(d, counter):
     for p in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
         with open(p) as f:
             for r in csv.DictReader(f):
-                if "k_build" in r["Kernel_Name"] and r["Counter_Name"] == counter:
+                # the builds: k_build, and k_keep for a steady-state build with GDP_TUNE_KEEP_KERNEL >= 1
+                if ("k_build" in r["Kernel_Name"] or "k_keep" in r["Kernel_Name"]) and r["Counter_Name"] == counter:
                     rows.append((int(r["Dispatch_Id"]), float(r["Counter_Value"]), r["Kernel_Name"]))
     rows.sort()
     return rows
@@ -127,6 +130,7 @@ def summarise(args):
                # so bench.py's roofline.traffic never takes it for the full build's record
                "op": "build_kept" if man.get("keep_zeros") else man.get("op", "build"),
                "keep_zeros": man.get("keep_zeros", 0),
+               "keep_kernel": man.get("keep_kernel", 0),
                "zero_window": man.get("zero_window", 0),
                **({"band_of": band_of, "band_rows": [r0, r1]} if band_of else {}),
                **({"image_stride_mb": man["image_stride_mb"]} if man.get("image_stride_mb") else {}),
@@ -141,7 +145,7 @@ def summarise(args):
                "correction": "read = 2 x FETCH_SIZE KiB (gfx950 half-count of wide streaming reads); write = WRITE_SIZE KiB"}
         tag = man["config"] + (f"b{band_of}" if band_of else "") + ("_subset" if man.get("op") == "subset" else "")
         zw = ("z1" if man.get("zero_window", 0) else "") + (f"s{man['image_stride_mb']}" if man.get("image_stride_mb") else "") \
-            + (f"k{man['pyramid_chunk_kb']}" if man.get("pyramid_chunk_kb") else "") + ("kept" if man.get("keep_zeros") else "")
+            + (f"k{man['pyramid_chunk_kb']}" if man.get("pyramid_chunk_kb") else "") + ("kept" if man.get("keep_zeros") else "") + (f"kk{man['keep_kernel']}" if man.get("keep_kernel") else "")
         out = os.path.join(REPO, "profiles", f"pmc_{tag}_v{m['variant']}o{m['tile_order']}{zw}_{args.round}.json")
         if os.path.exists(out) and not args.overwrite:
             print("keep", out)
@@ -165,6 +169,10 @@ def main():
     ap.add_argument("--keep-zeros", type=int, default=0, choices=[0, 1],
                     help="GDP_TUNE_KEEP_ZEROS: 0 (default) every counted build stores every byte; 1 the steady state "
                          "of a rebuilt context (records pmc_<cfg>_v<V>o<T>...kept_*.json, op build_kept)")
+    ap.add_argument("--keep-kernel", type=int, default=None, choices=[0, 1, 2],
+                    help="GDP_TUNE_KEEP_KERNEL of the steady-state builds (with --keep-zeros 1): 0 k_build's keep path, "
+                         "1 / 2 k_keep (records ...keptkk<N>_*.json, whose `kernel` names k_keep; the variant then only "
+                         "names the first, full build)")
     ap.add_argument("--variants", default=None, help="comma-separated variant numbers to profile (default: all)")
     ap.add_argument("--band-of", type=int, default=None,
                     help="row-band config: profile rank 0's band of N ranks (bench.py --gpus N --config c5's "
