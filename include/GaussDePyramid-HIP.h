@@ -91,6 +91,11 @@ public:
     // is neither published nor downloaded again.  At most the context's keypoint capacity (65536
     // unless gdp_set_keypoint_capacity(context(), n) raised it) records come back.
     std::vector<gdp_keypoint> DetectExtrema(float contrast_threshold = 0.f, float edge_ratio = 0.f);
+    // Extension: the keypoints of the last DetectExtrema localised to sub-sample precision on the
+    // device (gdp_refine_keypoints in gdp.h has the exact rule: quadratic fit, at most 5 moves,
+    // |interp| > contrast, the edge test when edge_ratio != 0), sorted like gdp_download_refined.
+    // Pending host edits of GaussPy are uploaded first; the pyramid itself is not changed.
+    std::vector<gdp_keypoint_refined> RefineKeypoints(float contrast = 0.f, float edge_ratio = 0.f);
     ~GaussPyramid_hip();
     bool initialized;
     bool mirror_host;  // GaussPy two-way: upload before / download after every mutating call (default true)
@@ -380,6 +385,20 @@ inline std::vector<gdp_keypoint> GaussPyramid_hip::DetectExtrema(float contrast_
     check_(ctx_, gdp_keypoint_count(ctx_, 0, &found), "DetectExtrema");
     std::vector<gdp_keypoint> out(found);
     check_(ctx_, gdp_download_keypoints(ctx_, 0, out.data(), out.size(), &stored, nullptr), "DetectExtrema");
+    out.resize(stored);
+    return out;
+}
+
+inline std::vector<gdp_keypoint_refined> GaussPyramid_hip::RefineKeypoints(float contrast, float edge_ratio) {
+    CallScope scope(this);
+    const bool clean = armed_;
+    pull_host_();
+    armed_ = clean;  // the refinement leaves the device pyramid alone, like the detection
+    check_(ctx_, gdp_refine_keypoints(ctx_, contrast, edge_ratio, nullptr), "RefineKeypoints");
+    size_t kept = 0, stored = 0;
+    check_(ctx_, gdp_refined_count(ctx_, 0, &kept), "RefineKeypoints");
+    std::vector<gdp_keypoint_refined> out(kept);
+    check_(ctx_, gdp_download_refined(ctx_, 0, out.data(), out.size(), &stored), "RefineKeypoints");
     out.resize(stored);
     return out;
 }

@@ -194,7 +194,8 @@ int gdp_device_input(const gdp_ctx* ctx, int b, const void** rows, size_t* pitch
  * a caller needs no host copy of the pyramid to find them.  It runs on whatever the pyramid
  * CURRENTLY holds (the context's own buffer or one bound with gdp_set_output_device): most
  * meaningful after gdp_build_gaussian, whose DoG is a real scale space, but the reference's window
- * pyramid works too.  Out of scope: sub-pixel refinement, orientation assignment, descriptors.
+ * pyramid works too.  gdp_refine_keypoints (below) localises them to sub-sample precision.  Out of
+ * scope: orientation assignment, descriptors.
  *
  * For image b and octave o (rows x cols as held by the context), levels 0..S+1 are taken as the
  * DoG levels D; level S+2 is never read.  Candidates are s in [1, S], r in [1, rows-2],
@@ -245,6 +246,81 @@ int gdp_download_keypoints(gdp_ctx* ctx, int b, gdp_keypoint* host, size_t capac
  * min(*count, capacity) valid, device order) and its counter.  GDP_ERR_STATE before the buffer
  * exists (first gdp_detect_extrema or gdp_set_keypoint_capacity). */
 int gdp_device_keypoints(const gdp_ctx* ctx, int b, const gdp_keypoint** records, const uint32_t** count);
+
+/* ---- extension: sub-pixel keypoint refinement on the device -----------------------------------
+ * Lowe's localisation step, done where the pyramid and the keypoint list already are (no reference
+ * counterpart, no parity claim): a 3-D quadratic is fitted to the DoG around every record of the
+ * context's keypoint list, the sample moves to its neighbour while the fitted extremum lies more
+ * than half a sample away, and low-contrast and edge-like points are rejected at the interpolated
+ * position.  It reads levels 0..S+1 of the CURRENT pyramid (own or bound); level S+2 is never read.
+ *
+ * The rule.  Every operation is a separately rounded float32 operation: no contraction, denormals
+ * kept, `/` is IEEE-correct division.  For a record (o, s, r, c), with D the levels of octave o
+ * (rows x cols), repeat at most GDP_REFINE_MAX_STEPS times:
+ *   v   = D[s][r][c]
+ *   gc  = (D[s][r][c+1] - D[s][r][c-1]) * 0.5f      gr, gs likewise along r and s
+ *   hcc = (D[s][r][c+1] + D[s][r][c-1]) - 2.0f*v    hrr, hss likewise
+ *   hrc = ((D[s][r+1][c+1] - D[s][r+1][c-1]) - (D[s][r-1][c+1] - D[s][r-1][c-1])) * 0.25f
+ *   hsc = ((D[s+1][r][c+1] - D[s+1][r][c-1]) - (D[s-1][r][c+1] - D[s-1][r][c-1])) * 0.25f
+ *   hsr = ((D[s+1][r+1][c] - D[s+1][r-1][c]) - (D[s-1][r+1][c] - D[s-1][r-1][c])) * 0.25f
+ *   A = hrr*hss - hsr*hsr   B = hrc*hss - hsc*hsr   C = hrc*hsr - hsc*hrr
+ *   E = hcc*hss - hsc*hsc   Q = hcc*hsr - hrc*hsc   G = hcc*hrr - hrc*hrc
+ *   det = (hcc*A - hrc*B) + hsc*C
+ *   reject unless fabsf(det) > 0.0f                       (zero or NaN)
+ *   xc = -(((A*gc - B*gr) + C*gs) / det)
+ *   xr = -(((E*gr - B*gc) - Q*gs) / det)
+ *   xs = -(((C*gc - Q*gr) + G*gs) / det)
+ *   if fabsf(xc) <= 0.5f && fabsf(xr) <= 0.5f && fabsf(xs) <= 0.5f:  converged, stop
+ *   c += (xc > 0.5f) - (xc < -0.5f); same for r with xr and s with xs   (one sample per axis and step)
+ *   reject if nothing moved (a NaN offset), or if now s<1 || s>S || r<1 || r>rows-2 || c<1 || c>cols-2
+ * A record that has not converged after GDP_REFINE_MAX_STEPS solves is rejected.  At convergence
+ *   interp = v + ((gc*xc + gr*xr) + gs*xs) * 0.5f
+ * and the record is kept when fabsf(interp) > contrast_threshold (a NaN fails) and, when
+ * edge_ratio != 0, it also passes the edge test of gdp_detect_extrema (3. above) with dxx = hcc,
+ * dyy = hrr, dxy = hrc taken at the final sample.  The kept record holds the final (s, r, c), v,
+ * (xs, xr, xc), interp and the input's kind.  Two inputs that end at the same sample both stay, as
+ * identical records: the result is an exact multiset.  A consumer's image coordinates are
+ * (col + dcol) * 2^octave and (row + drow) * 2^octave. */
+typedef struct gdp_keypoint_refined {   /* 32 bytes */
+    uint16_t octave; uint8_t scale; int8_t kind;  /* kind copied from the input record */
+    int32_t row, col;                             /* the FINAL sample (after moves) */
+    float value;                                  /* D[scale][row][col] at the final sample */
+    float dscale, drow, dcol;                     /* offset from the final sample, each |.| <= 0.5 */
+    float interp;                                 /* interpolated DoG value at the offset */
+} gdp_keypoint_refined;   /* its first 16 bytes are a gdp_keypoint at the final sample */
+#define GDP_REFINE_MAX_STEPS 5
+/* Refine every image's keypoint list: the first min(counter, keypoint capacity) records, read on
+ * the device — the host never reads the counter, so launching this right after gdp_detect_extrema
+ * on the same stream is the normal use (the caller orders the two when the streams differ).
+ * Asynchronous and stream-ordered: zeroes the refined counters on `stream`, then ONE launch.  The
+ * survivors are appended to a context-owned [batch][keypoint capacity] refined buffer with [batch]
+ * uint32 counters, allocated on first use (gdp_set_keypoint_capacity drops and reallocates it with
+ * the keypoint buffer); outputs never exceed inputs, so it cannot overflow.  The device order is
+ * unspecified.  The keypoint list itself is not changed, and gdp_detect_extrema leaves the refined
+ * results alone: they stay those of the last refinement.  Arguments as for gdp_detect_extrema:
+ * contrast_threshold >= 0 (not NaN), edge_ratio 0 or finite and >= 1, else GDP_ERR_ARG; row-band
+ * contexts GDP_ERR_STATE; GDP_ERR_STATE too before a keypoint buffer exists (gdp_device_keypoints'
+ * condition).  The pyramid is only read, but this call, gdp_refined_count, gdp_download_refined
+ * and gdp_upload_keypoints count as pyramid writers for GDP_TUNE_KEEP_ZEROS (exports are writers
+ * unless listed otherwise): the gdp_build that follows one of them stores every byte. */
+int gdp_refine_keypoints(gdp_ctx* ctx, float contrast_threshold, float edge_ratio, void* stream);
+/* Records the last refinement kept in image b (blocking; waits for the context's OWN stream; 0
+ * before any refinement). */
+int gdp_refined_count(gdp_ctx* ctx, int b, size_t* kept);
+/* Copy min(kept, `capacity`) refined records of image b to `host` (blocking), sorted ascending by
+ * (octave, scale, row, col), then by the bit patterns of (dscale, drow, dcol, interp, value, kind),
+ * so host results are the same run to run.  *stored = records written (may be NULL). */
+int gdp_download_refined(gdp_ctx* ctx, int b, gdp_keypoint_refined* host, size_t capacity, size_t* stored);
+/* Zero-copy view for device consumers: image b's refined records (capacity records, the first
+ * *count valid, device order) and its counter.  GDP_ERR_STATE before the first refinement. */
+int gdp_device_refined(const gdp_ctx* ctx, int b, const gdp_keypoint_refined** records, const uint32_t** count);
+/* Make host[0..n) image b's keypoint list and set its counter to n (blocking; allocates the
+ * keypoint buffer if needed): the state restore for the list, as gdp_upload_pyramid is for the
+ * pyramid, and the way to refine points of the caller's own.  Every record is validated on the
+ * host — octave < octaves, scale in [1, S], row in [1, rows-2], col in [1, cols-2], kind +1 or -1
+ * (`value` is not used), n <= the keypoint capacity; anything else is GDP_ERR_ARG and changes
+ * nothing. */
+int gdp_upload_keypoints(gdp_ctx* ctx, int b, const gdp_keypoint* host, size_t n);
 
 /* ---- output --------------------------------------------------------------------------------
  * The blocking copies below are ordered after work on the context's OWN stream; if a build was

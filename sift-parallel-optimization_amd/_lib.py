@@ -119,6 +119,11 @@ SIGNATURES = {
     "gdp_keypoint_count": (_c_int, [_p, _c_int, ctypes.POINTER(_c_size)]),
     "gdp_download_keypoints": (_c_int, [_p, _c_int, _p, _c_size, ctypes.POINTER(_c_size), ctypes.POINTER(_c_size)]),
     "gdp_device_keypoints": (_c_int, [_p, _c_int, _pp, _pp]),
+    "gdp_refine_keypoints": (_c_int, [_p, ctypes.c_float, ctypes.c_float, _p]),
+    "gdp_refined_count": (_c_int, [_p, _c_int, ctypes.POINTER(_c_size)]),
+    "gdp_download_refined": (_c_int, [_p, _c_int, _p, _c_size, ctypes.POINTER(_c_size)]),
+    "gdp_device_refined": (_c_int, [_p, _c_int, _pp, _pp]),
+    "gdp_upload_keypoints": (_c_int, [_p, _c_int, _p, _c_size]),
     "gdp_checksum": (_c_int, [_p, _c_int, ctypes.POINTER(ctypes.c_uint64)]),
     "gdp_get_taps": (_c_int, [_p, _c_int, _c_int, _c_int, _p]),
     "gdp_set_window_centre": (_c_int, [_p, _c_int]),

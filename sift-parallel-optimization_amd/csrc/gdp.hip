@@ -54,6 +54,7 @@ namespace {
 #include "gdp_inplace.inc"
 #include "gdp_conv.inc"
 #include "gdp_extrema.inc"
+#include "gdp_refine.inc"
 #include "gdp_util.inc"
 #include "gdp_track.inc"
 
@@ -178,6 +179,9 @@ struct gdp_ctx {
     gdp_keypoint* d_kp = nullptr;
     uint32_t* d_kp_count = nullptr;
     size_t kp_capacity = 65536;   // gdp_set_keypoint_capacity: records per image
+    // gdp_refine_keypoints: [batch][kp_capacity] refined records and [batch] counters, allocated on first use
+    gdp_keypoint_refined* d_rf = nullptr;
+    uint32_t* d_rf_count = nullptr;
     std::vector<float> h_taps;
     long long in_pitch_own = 0, in_img_stride_own = 0;
     hipStream_t stream = nullptr;
@@ -1222,6 +1226,8 @@ void gdp_destroy(gdp_ctx* c) {
     if (c->d_sum) (void)hipFree(c->d_sum);
     if (c->d_kp) (void)hipFree(c->d_kp);
     if (c->d_kp_count) (void)hipFree(c->d_kp_count);
+    if (c->d_rf) (void)hipFree(c->d_rf);
+    if (c->d_rf_count) (void)hipFree(c->d_rf_count);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -2604,6 +2610,26 @@ static int ensure_keypoints(gdp_ctx* c) {
     return GDP_OK;
 }
 
+// gdp_refine_keypoints' outputs: [batch][kp_capacity] 32-byte records and [batch] counters
+static int ensure_refined(gdp_ctx* c) {
+    if (c->d_rf && c->d_rf_count) return GDP_OK;
+    const size_t batch = (size_t)c->geom.batch;
+    hipError_t e = hipSuccess;
+    if (c->kp_capacity > (SIZE_MAX / sizeof(gdp_keypoint_refined)) / batch) e = hipErrorOutOfMemory;
+    if (e == hipSuccess && !c->d_rf)
+        e = hipMalloc(reinterpret_cast<void**>(&c->d_rf), c->kp_capacity * batch * sizeof(gdp_keypoint_refined));
+    if (e == hipSuccess && !c->d_rf_count) {
+        e = hipMalloc(reinterpret_cast<void**>(&c->d_rf_count), batch * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemset(c->d_rf_count, 0, batch * sizeof(uint32_t));
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return c->status(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, "refined keypoint buffer (%zu records x %zu images): %s",
+                         c->kp_capacity, batch, hipGetErrorString(e));
+    }
+    return GDP_OK;
+}
+
 int gdp_set_keypoint_capacity(gdp_ctx* c, size_t per_image) try {
     GDP_READS_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
@@ -2611,19 +2637,25 @@ int gdp_set_keypoint_capacity(gdp_ctx* c, size_t per_image) try {
         return c->status(GDP_ERR_ARG, "gdp_set_keypoint_capacity: capacity must be > 0 and fit the address space");
     if (per_image == c->kp_capacity && c->d_kp) return GDP_OK;
     GDP_HIP(c, hipSetDevice(c->device));
-    if (c->d_kp) {
+    const bool had_refined = c->d_rf != nullptr;
+    if (c->d_kp || c->d_rf) {
         // a configuration-time event like a geometry change: no launch in flight may still write
-        // the old buffer
+        // the old buffers
         GDP_HIP(c, hipDeviceSynchronize());
-        GDP_HIP(c, hipFree(c->d_kp));
+        if (c->d_kp) GDP_HIP(c, hipFree(c->d_kp));
         c->d_kp = nullptr;
+        if (c->d_rf) GDP_HIP(c, hipFree(c->d_rf));
+        c->d_rf = nullptr;
     }
     c->kp_capacity = per_image;
     if (c->d_kp_count) {  // the old records are gone: nothing found until the next detection
         GDP_HIP(c, hipMemsetAsync(c->d_kp_count, 0, (size_t)c->geom.batch * sizeof(uint32_t), c->stream));
+        if (c->d_rf_count) GDP_HIP(c, hipMemsetAsync(c->d_rf_count, 0, (size_t)c->geom.batch * sizeof(uint32_t), c->stream));
         GDP_HIP(c, hipStreamSynchronize(c->stream));
     }
-    return ensure_keypoints(c);
+    const int rc = ensure_keypoints(c);
+    if (rc != GDP_OK || !had_refined) return rc;
+    return ensure_refined(c);  // the refined buffer follows the keypoint capacity
 } GDP_ABI_CATCH(c)
 
 int gdp_detect_extrema(gdp_ctx* c, float contrast_threshold, float edge_ratio, void* stream) try {
@@ -2709,6 +2741,130 @@ int gdp_device_keypoints(const gdp_ctx* c, int b, const gdp_keypoint** records, 
     }
     if (records) *records = c->d_kp + (size_t)b * c->kp_capacity;
     if (count) *count = c->d_kp_count + b;
+    return GDP_OK;
+} GDP_ABI_CATCH(c)
+
+// ---- extension: sub-pixel refinement of the keypoint list (gdp_refine.inc) -----------------------
+// The four exports below only read the pyramid; they carry the writers' marker because the
+// read-only list is an explicit one (tests/test_keep_zeros_abi.py) and new exports are denied by
+// default: the build that follows them stores every byte.
+int gdp_refine_keypoints(gdp_ctx* c, float contrast_threshold, float edge_ratio, void* stream) try {
+    GDP_WRITES_PYRAMID(c);
+    if (!c) return GDP_ERR_ARG;
+    if (!(contrast_threshold >= 0.0f))
+        return c->status(GDP_ERR_ARG, "gdp_refine_keypoints: contrast_threshold must be >= 0");
+    if (edge_ratio != 0.0f && !(edge_ratio >= 1.0f && std::isfinite(edge_ratio)))
+        return c->status(GDP_ERR_ARG, "gdp_refine_keypoints: edge_ratio must be 0 (no edge test) or finite and >= 1");
+    const Geom& g = c->geom;
+    if (g.in_row0 != 0 || g.in_rows != g.H)
+        return c->status(GDP_ERR_STATE, "gdp_refine_keypoints: a row band does not hold its keypoints' neighbours "
+                                        "across the band edges; refine on a whole-image context");
+    if (!c->d_kp || !c->d_kp_count)
+        return c->status(GDP_ERR_STATE, "gdp_refine_keypoints: no keypoint list yet (run gdp_detect_extrema or "
+                                        "gdp_upload_keypoints first)");
+    const unsigned long long per_img = ((unsigned long long)c->kp_capacity + kRfBlock - 1) / kRfBlock;
+    if (per_img * (unsigned long long)g.batch >= (1ull << 31))
+        return c->status(GDP_ERR_ARG, "gdp_refine_keypoints: keypoint capacity too large for one launch");
+    GDP_HIP(c, hipSetDevice(c->device));
+    const int rc = ensure_refined(c);
+    if (rc != GDP_OK) return rc;
+    hipStream_t st = c->pick(stream);
+    GDP_HIP(c, hipMemsetAsync(c->d_rf_count, 0, (size_t)g.batch * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_refine, dim3((unsigned)(per_img * g.batch)), dim3(kRfBlock), 0, st, c->d_geom, c->d_out,
+                       reinterpret_cast<const uint4*>(c->d_kp), c->d_kp_count, reinterpret_cast<uint4*>(c->d_rf), c->d_rf_count,
+                       (unsigned long long)c->kp_capacity, (unsigned)per_img, contrast_threshold, edge_ratio);
+    GDP_HIP(c, hipGetLastError());
+    return GDP_OK;
+} GDP_ABI_CATCH(c)
+
+int gdp_refined_count(gdp_ctx* c, int b, size_t* kept) try {
+    GDP_WRITES_PYRAMID(c);
+    if (!c || !kept || b < 0 || b >= c->geom.batch)
+        return c ? c->status(GDP_ERR_ARG, "gdp_refined_count: bad argument") : GDP_ERR_ARG;
+    *kept = 0;
+    if (!c->d_rf_count) return GDP_OK;  // no refinement has run
+    GDP_HIP(c, hipSetDevice(c->device));
+    uint32_t n = 0;
+    GDP_HIP(c, hipMemcpyAsync(&n, c->d_rf_count + b, sizeof n, hipMemcpyDeviceToHost, c->stream));
+    GDP_HIP(c, hipStreamSynchronize(c->stream));
+    *kept = n;
+    return GDP_OK;
+} GDP_ABI_CATCH(c)
+
+int gdp_download_refined(gdp_ctx* c, int b, gdp_keypoint_refined* host, size_t capacity, size_t* stored) try {
+    GDP_WRITES_PYRAMID(c);
+    if (!c || b < 0 || b >= c->geom.batch || (!host && capacity))
+        return c ? c->status(GDP_ERR_ARG, "gdp_download_refined: bad argument") : GDP_ERR_ARG;
+    if (stored) *stored = 0;
+    size_t total = 0;
+    const int rc = gdp_refined_count(c, b, &total);
+    if (rc != GDP_OK) return rc;
+    const size_t n = std::min(total, std::min(c->kp_capacity, capacity));
+    if (n == 0 || !c->d_rf) return GDP_OK;
+    GDP_SETTLE(c, "gdp_download_refined", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint_refined)); });
+    GDP_HIP(c, hipMemcpyAsync(track_dma_ptr(host), c->d_rf + (size_t)b * c->kp_capacity, n * sizeof(gdp_keypoint_refined),
+                              hipMemcpyDeviceToHost, c->stream));
+    GDP_HIP(c, hipStreamSynchronize(c->stream));
+    // the device order depends on the waves' timing, and two inputs may end at the same sample:
+    // the position first, then the bits of everything else, so equal keys are identical records
+    auto bits = [](float f) {
+        uint32_t u;
+        std::memcpy(&u, &f, sizeof u);
+        return u;
+    };
+    std::sort(host, host + n, [&](const gdp_keypoint_refined& p, const gdp_keypoint_refined& q) {
+        if (p.octave != q.octave) return p.octave < q.octave;
+        if (p.scale != q.scale) return p.scale < q.scale;
+        if (p.row != q.row) return p.row < q.row;
+        if (p.col != q.col) return p.col < q.col;
+        if (bits(p.dscale) != bits(q.dscale)) return bits(p.dscale) < bits(q.dscale);
+        if (bits(p.drow) != bits(q.drow)) return bits(p.drow) < bits(q.drow);
+        if (bits(p.dcol) != bits(q.dcol)) return bits(p.dcol) < bits(q.dcol);
+        if (bits(p.interp) != bits(q.interp)) return bits(p.interp) < bits(q.interp);
+        if (bits(p.value) != bits(q.value)) return bits(p.value) < bits(q.value);
+        return (uint8_t)p.kind < (uint8_t)q.kind;
+    });
+    if (stored) *stored = n;
+    return GDP_OK;
+} GDP_ABI_CATCH(c)
+
+int gdp_device_refined(const gdp_ctx* c, int b, const gdp_keypoint_refined** records, const uint32_t** count) try {
+    if (!c || b < 0 || b >= c->geom.batch) return GDP_ERR_ARG;
+    if (!c->d_rf || !c->d_rf_count) {
+        const_cast<gdp_ctx*>(c)->status(GDP_ERR_STATE, "gdp_device_refined: no refined buffer yet (run gdp_refine_keypoints first)");
+        return GDP_ERR_STATE;
+    }
+    if (records) *records = c->d_rf + (size_t)b * c->kp_capacity;
+    if (count) *count = c->d_rf_count + b;
+    return GDP_OK;
+} GDP_ABI_CATCH(c)
+
+int gdp_upload_keypoints(gdp_ctx* c, int b, const gdp_keypoint* host, size_t n) try {
+    GDP_WRITES_PYRAMID(c);
+    if (!c || b < 0 || b >= c->geom.batch || (!host && n))
+        return c ? c->status(GDP_ERR_ARG, "gdp_upload_keypoints: bad argument") : GDP_ERR_ARG;
+    const Geom& g = c->geom;
+    if (n > c->kp_capacity)
+        return c->status(GDP_ERR_ARG, "gdp_upload_keypoints: %zu records exceed the keypoint capacity %zu", n, c->kp_capacity);
+    GDP_HIP(c, hipSetDevice(c->device));
+    if (n) GDP_SETTLE(c, "gdp_upload_keypoints", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint)); });
+    for (size_t i = 0; i < n; ++i) {
+        const gdp_keypoint& k = host[i];
+        const bool ok = (int)k.octave < g.O && k.scale >= 1 && (int)k.scale <= g.S && k.row >= 1 &&
+                        k.row <= g.oct[std::min<int>(k.octave, g.O - 1)].rows - 2 && k.col >= 1 &&
+                        k.col <= g.oct[std::min<int>(k.octave, g.O - 1)].cols - 2 && (k.kind == 1 || k.kind == -1);
+        if (!ok)
+            return c->status(GDP_ERR_ARG, "gdp_upload_keypoints: record %zu (octave %d, scale %d, row %d, col %d, kind %d) is no "
+                                          "candidate of this context", i, (int)k.octave, (int)k.scale, (int)k.row, (int)k.col, (int)k.kind);
+    }
+    const int rc = ensure_keypoints(c);
+    if (rc != GDP_OK) return rc;
+    const uint32_t count = (uint32_t)n;
+    if (n)
+        GDP_HIP(c, hipMemcpyAsync(c->d_kp + (size_t)b * c->kp_capacity, track_dma_ptr(host), n * sizeof(gdp_keypoint),
+                                  hipMemcpyHostToDevice, c->stream));
+    GDP_HIP(c, hipMemcpyAsync(c->d_kp_count + b, &count, sizeof count, hipMemcpyHostToDevice, c->stream));
+    GDP_HIP(c, hipStreamSynchronize(c->stream));
     return GDP_OK;
 } GDP_ABI_CATCH(c)
 

@@ -60,6 +60,13 @@ KEYPOINT_DTYPE = np.dtype({"names": ["octave", "scale", "kind", "row", "col", "v
                            "offsets": [0, 2, 3, 4, 8, 12], "itemsize": 16})
 
 
+# struct gdp_keypoint_refined (include/gdp.h): 32 bytes, the first 16 a gdp_keypoint at the final sample
+REFINED_DTYPE = np.dtype({"names": ["octave", "scale", "kind", "row", "col", "value", "dscale", "drow", "dcol", "interp"],
+                          "formats": [np.uint16, np.uint8, np.int8, np.int32, np.int32, np.float32, np.float32,
+                                      np.float32, np.float32, np.float32],
+                          "offsets": [0, 2, 3, 4, 8, 12, 16, 20, 24, 28], "itemsize": 32})
+
+
 class Keypoints(np.ndarray):
     """A KEYPOINT_DTYPE array of the stored records with `found`, the number the detection counted
     (larger than len() when the context's capacity was too small)."""
@@ -453,6 +460,41 @@ class PyramidContext:
         check(lib().gdp_device_keypoints(self._ctx, int(b), ctypes.byref(recs), ctypes.byref(count)), self._ctx)
         return recs.value, count.value
 
+    def refine_keypoints(self, contrast=0.0, edge_ratio=0.0, stream=None):
+        """Localise image by image the records of the keypoint list (the last detect_extrema's, or
+        upload_keypoints') to sub-sample precision on the CURRENT pyramid (gdp_refine_keypoints:
+        quadratic fit, at most 5 moves, |interp| > contrast, and the edge test when edge_ratio
+        != 0); asynchronous on `stream`, one launch, no host read of the counter."""
+        check(lib().gdp_refine_keypoints(self._ctx, float(contrast), float(edge_ratio), _stream_handle(stream)),
+              self._ctx)
+
+    def refined_count(self, b=0):
+        """Records the last refinement kept in image b (blocking)."""
+        n = ctypes.c_size_t()
+        check(lib().gdp_refined_count(self._ctx, int(b), ctypes.byref(n)), self._ctx)
+        return n.value
+
+    def refined_keypoints(self, b=0):
+        """The refined records of image b as a REFINED_DTYPE array sorted by (octave, scale, row,
+        col) and then by the bits of the other fields (blocking)."""
+        out = np.zeros(self.refined_count(b), REFINED_DTYPE)
+        stored = ctypes.c_size_t()
+        check(lib().gdp_download_refined(self._ctx, int(b), _ptr(out) if out.size else None, out.size,
+                                         ctypes.byref(stored)), self._ctx)
+        return out[:stored.value]
+
+    def device_refined(self, b=0):
+        """(device address of image b's refined records, device address of its uint32 counter)."""
+        recs, count = ctypes.c_void_p(), ctypes.c_void_p()
+        check(lib().gdp_device_refined(self._ctx, int(b), ctypes.byref(recs), ctypes.byref(count)), self._ctx)
+        return recs.value, count.value
+
+    def upload_keypoints(self, records, b=0):
+        """Make `records` (KEYPOINT_DTYPE, or anything numpy converts to it) image b's keypoint
+        list (blocking; gdp_upload_keypoints validates every record)."""
+        recs = np.ascontiguousarray(records, dtype=KEYPOINT_DTYPE).reshape(-1)
+        check(lib().gdp_upload_keypoints(self._ctx, int(b), _ptr(recs) if recs.size else None, recs.size), self._ctx)
+
     def device_level_ptr(self, b, o, s):
         """Device address of level (o, s) of image b.  Read-only: after writing through it, call
         pyramid_written() before the next build."""
@@ -589,6 +631,14 @@ class GaussPyramid:
         self.SyncDevice()
         self._ctx.detect_extrema(contrast, edge_ratio)
         return self._ctx.keypoints(0)
+
+    def RefineKeypoints(self, contrast=0.0, edge_ratio=0.0):
+        """Extension: refine the last DetectExtrema's keypoints to sub-sample precision on the
+        device (PyramidContext.refine_keypoints) and return them as a REFINED_DTYPE array.  Host
+        edits to GaussPy are refined on; the pyramid is not changed."""
+        self.SyncDevice()
+        self._ctx.refine_keypoints(contrast, edge_ratio)
+        return self._ctx.refined_keypoints(0)
 
     def output(self, file=None):
         """:89-104 — print scale 0 of each octave (space separated) and an `==` separator row."""
