@@ -300,9 +300,7 @@ typedef struct gdp_keypoint_refined {   /* 32 bytes */
  * results alone: they stay those of the last refinement.  Arguments as for gdp_detect_extrema:
  * contrast_threshold >= 0 (not NaN), edge_ratio 0 or finite and >= 1, else GDP_ERR_ARG; row-band
  * contexts GDP_ERR_STATE; GDP_ERR_STATE too before a keypoint buffer exists (gdp_device_keypoints'
- * condition).  The pyramid is only read, but this call, gdp_refined_count, gdp_download_refined
- * and gdp_upload_keypoints count as pyramid writers for GDP_TUNE_KEEP_ZEROS (exports are writers
- * unless listed otherwise): the gdp_build that follows one of them stores every byte. */
+ * condition).  The pyramid is only read. */
 int gdp_refine_keypoints(gdp_ctx* ctx, float contrast_threshold, float edge_ratio, void* stream);
 /* Records the last refinement kept in image b (blocking; waits for the context's OWN stream; 0
  * before any refinement). */

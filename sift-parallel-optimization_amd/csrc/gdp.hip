@@ -2745,11 +2745,10 @@ int gdp_device_keypoints(const gdp_ctx* c, int b, const gdp_keypoint** records, 
 } GDP_ABI_CATCH(c)
 
 // ---- extension: sub-pixel refinement of the keypoint list (gdp_refine.inc) -----------------------
-// The four exports below only read the pyramid; they carry the writers' marker because the
-// read-only list is an explicit one (tests/test_keep_zeros_abi.py) and new exports are denied by
-// default: the build that follows them stores every byte.
+// The four exports below only read the pyramid (k_refine takes it const; the buffers they write are
+// the keypoint lists'): they are on the read-only list, so the build that follows them is a kept one.
 int gdp_refine_keypoints(gdp_ctx* c, float contrast_threshold, float edge_ratio, void* stream) try {
-    GDP_WRITES_PYRAMID(c);
+    GDP_READS_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
     if (!(contrast_threshold >= 0.0f))
         return c->status(GDP_ERR_ARG, "gdp_refine_keypoints: contrast_threshold must be >= 0");
@@ -2778,7 +2777,7 @@ int gdp_refine_keypoints(gdp_ctx* c, float contrast_threshold, float edge_ratio,
 } GDP_ABI_CATCH(c)
 
 int gdp_refined_count(gdp_ctx* c, int b, size_t* kept) try {
-    GDP_WRITES_PYRAMID(c);
+    GDP_READS_PYRAMID(c);
     if (!c || !kept || b < 0 || b >= c->geom.batch)
         return c ? c->status(GDP_ERR_ARG, "gdp_refined_count: bad argument") : GDP_ERR_ARG;
     *kept = 0;
@@ -2792,7 +2791,7 @@ int gdp_refined_count(gdp_ctx* c, int b, size_t* kept) try {
 } GDP_ABI_CATCH(c)
 
 int gdp_download_refined(gdp_ctx* c, int b, gdp_keypoint_refined* host, size_t capacity, size_t* stored) try {
-    GDP_WRITES_PYRAMID(c);
+    GDP_READS_PYRAMID(c);
     if (!c || b < 0 || b >= c->geom.batch || (!host && capacity))
         return c ? c->status(GDP_ERR_ARG, "gdp_download_refined: bad argument") : GDP_ERR_ARG;
     if (stored) *stored = 0;
@@ -2840,7 +2839,7 @@ int gdp_device_refined(const gdp_ctx* c, int b, const gdp_keypoint_refined** rec
 } GDP_ABI_CATCH(c)
 
 int gdp_upload_keypoints(gdp_ctx* c, int b, const gdp_keypoint* host, size_t n) try {
-    GDP_WRITES_PYRAMID(c);
+    GDP_READS_PYRAMID(c);
     if (!c || b < 0 || b >= c->geom.batch || (!host && n))
         return c ? c->status(GDP_ERR_ARG, "gdp_upload_keypoints: bad argument") : GDP_ERR_ARG;
     const Geom& g = c->geom;

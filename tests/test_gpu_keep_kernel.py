@@ -21,12 +21,15 @@ rebuild (after image A, whose signs are the opposite) of a clean context — wit
   1024 x 512        two row bands (row0 != 0)
   uint8 input       level S+2 is +0 everywhere outside the support
   bound device input with a pitch that is no multiple of 4: no vector loads, not eligible
+The last tests name the paths that tests/test_gpu_steady_fuzz.py draws at random, so a regression
+names itself without a seed: the grid-stride loop under a grid cap (tail units included), plain
+stores (nontemporal = 0), the input format switched between kept builds, and the smallest shapes
+with every octave count.
 Runs on an MI355X.
 """
-import ctypes
-
 import numpy as np
 import pytest
+from steady_cases import _poison, _skipped, _support  # the store map of a kept build, shared with the sweep
 
 pytestmark = pytest.mark.gpu
 
@@ -59,38 +62,6 @@ def _images(oracle, H, W, seed=12345):
     b[rng.integers(0, H, 100), rng.integers(0, W, 100)] = INT32_MIN
     b[0, 0], b[-1, -1] = -1, -1  # corners far outside every support: sign bit only
     return a, b
-
-
-def _support(oracle, H, W, O, S):
-    """Per octave: (rows, cols) boolean masks of the window support — some tap of some scale,
-    under either window centre, is non-zero."""
-    out = []
-    for o in range(O):
-        masks = []
-        for n in (H, W):
-            m = np.zeros(n >> o, bool)
-            for centre in ("serial", "intlen"):
-                for s in range(S + 3):
-                    t = oracle.taps(n, o, s, centre)[:n >> o]
-                    m[:t.size] |= t != 0
-            masks.append(m)
-        out.append(tuple(masks))
-    return out
-
-
-def _skipped(oracle, H, W, O, S, dims):
-    """Per octave, the pixels whose DoG stores a kept build skips: rows outside the row support,
-    and 4-pixel groups wholly outside the column support.  `dims`: the context's level_dims per
-    octave (rows held, cols, first global row)."""
-    out = []
-    for o, (rows, cols) in enumerate(_support(oracle, H, W, O, S)):
-        n = cols.size
-        grp = np.zeros(n, bool)
-        for c in range(0, n, 4):
-            grp[c:c + 4] = not cols[c:c + 4].any()
-        nrows, _, first = dims[o]
-        out.append(~rows[first:first + nrows, None] | grp[None, :])
-    return out
 
 
 def _want_levels(oracle, ctx, img, H, W, S, O):
@@ -190,16 +161,6 @@ def test_bound_input_without_vector_loads_is_not_taken(pkg, oracle):
             ctx.build()
             ctx.sync()
             _check_levels(ctx, 0, want, S, O, ("unbound", kern))
-
-
-def _poison(ctx):
-    """0xFF over the whole context-owned pyramid, behind the library's back."""
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipMemset.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t]
-    hip.hipDeviceSynchronize.argtypes = []
-    ctx.sync()
-    assert hip.hipMemset(ctypes.c_void_p(ctx.device_level_ptr(0, 0, 0)), 0xFF, ctx.pyramid_bytes()) == 0
-    assert hip.hipDeviceSynchronize() == 0
 
 
 @pytest.mark.parametrize("name", ["200x1028", "band_hi"])
@@ -318,3 +279,127 @@ def test_time_builds_and_autotune_leave_a_correct_pyramid(pkg, oracle):
         ctx.upload_pyramid(np.full(ctx.packed_floats(), np.nan, np.float32))
         ctx.autotune(iters=1)
         _check_levels(ctx, 0, want, S, O, "autotune")
+
+
+# ---- fixed-name cases of the paths the steady-state sweep (test_gpu_steady_fuzz.py) draws at random --
+_WANTS = {}  # (name, image of the batch) -> the oracle's levels of the rebuild's image: computed once, never modified
+
+
+def _kept_rebuild(pkg, oracle, name, what, **tuning):
+    """Image A, then image B on the same (clean) context under `tuning`; the kept rebuild must be
+    the oracle's build of B in every level of every image."""
+    H, W, O, S, kw = CASES[name]
+    B = kw.get("batch", 1)
+    pair = _case_images(oracle, name)
+    seq = [[pair[(k + i) % 2] for i in range(B)] for k in range(2)]
+    with pkg.PyramidContext(H, W, S=S, octaves=O, **kw) as ctx:
+        ctx.set_tuning(**tuning)
+        for k in range(2):
+            for i in range(B):
+                ctx.set_input(seq[k][i], i)
+            assert ctx.tuning()["zeros_clean"] == k
+            ctx.build()
+        assert ctx.tuning()["zeros_clean"] == 1
+        ctx.sync()
+        for i in range(B):
+            if (name, i) not in _WANTS:
+                _WANTS[(name, i)] = _want_levels(oracle, ctx, seq[1][i], H, W, S, O)
+            _check_levels(ctx, i, _WANTS[(name, i)], S, O, (name, what, tuning))
+
+
+GRID_CASES = ("200x1028", "64x2048_o7", "96x768_b3")
+# 200x1028: 65 tiles; 64x2048_o7: 32 tiles and the tail units of octaves 5 and 6; 96x768_b3: 54 tiles of 3 images
+GRID_CAPS = {"grid1": dict(grid=1), "grid3": dict(grid=3), "blocks_per_cu1": dict(blocks_per_cu=1)}
+
+
+@pytest.mark.parametrize("cap", sorted(GRID_CAPS))
+@pytest.mark.parametrize("kern", KERNELS)
+@pytest.mark.parametrize("name", GRID_CASES)
+def test_grid_capped_keep_kernel_rebuild_is_the_oracle(pkg, oracle, name, kern, cap):
+    """k_keep's grid-stride loop: with GDP_TUNE_GRID = 1 / 3 one block walks every unit (a third of
+    them), tiles of every image and — 64x2048_o7 — the tail units after them; blocks_per_cu = 1 caps
+    the grid at one block per CU."""
+    _kept_rebuild(pkg, oracle, name, cap, keep_kernel=kern, **GRID_CAPS[cap])
+
+
+@pytest.mark.parametrize("kern", KERNELS)
+@pytest.mark.parametrize("name", GRID_CASES)
+def test_keep_kernel_with_plain_stores_is_the_oracle(pkg, oracle, name, kern):
+    """nontemporal = 0 launches k_keep<false, *>: the same bits through plain stores."""
+    _kept_rebuild(pkg, oracle, name, "nontemporal=0", keep_kernel=kern, nontemporal=0)
+    _kept_rebuild(pkg, oracle, name, "nontemporal=0, grid=3", keep_kernel=kern, nontemporal=0, grid=3)
+
+
+@pytest.mark.parametrize("kern", (0,) + KERNELS)
+def test_input_format_switches_between_kept_builds(pkg, oracle, kern):
+    """int32 -> uint8 -> int32 across three kept builds, the int32 images mostly negative: the
+    uint8 build owes +0 in all of level S+2 outside the support (inside it the level is the last
+    Gaussian of pixels >= 0: no sign bit anywhere) — it must overwrite the -0 the int32 build left,
+    a kernel that stored nothing for uint8 input would leave them — and the int32 build after it
+    the oracle's signs again."""
+    H, W, O, S, _ = CASES["200x1028"]
+    first, _ = _case_images(oracle, "200x1028")
+    rng = np.random.default_rng(77)
+    neg = [-(rng.integers(1, 2**31 - 1, size=(H, W), dtype=np.int64)).astype(np.int32) for _ in range(2)]
+    for n in neg:
+        n[rng.integers(0, H, 300), rng.integers(0, W, 300)] = 0
+        n[rng.integers(0, H, 300), rng.integers(0, W, 300)] = 5
+        n[rng.integers(0, H, 100), rng.integers(0, W, 100)] = INT32_MIN
+    u8 = rng.integers(0, 256, size=(H, W), dtype=np.int64).astype(np.uint8)
+    support = _support(oracle, H, W, O, S)
+    with pkg.PyramidContext(H, W, S=S, octaves=O) as ctx:
+        ctx.set_tuning(keep_kernel=kern)
+        ctx.set_input(first)
+        ctx.build()
+        for step, (fmt, img) in enumerate([("i32", neg[0]), ("u8", u8), ("i32", neg[1])]):
+            ctx.set_input_format(fmt)
+            assert ctx.tuning()["zeros_clean"] == 1, (step, "the input format is not the pyramid")
+            ctx.set_input(img)
+            ctx.build()
+            assert ctx.tuning()["zeros_clean"] == 1
+            ctx.sync()
+            want = _want_levels(oracle, ctx, img, H, W, S, O)
+            for o in range(O):
+                top, w = _bits(ctx.level(0, o, S + 2)), _bits(want[o * (S + 3) + S + 2])
+                if fmt == "u8":
+                    rows, cols = support[o]
+                    outside = ~(rows[:, None] & cols[None, :])
+                    assert outside.mean() > 0.5 or o >= 3
+                    assert not top[outside].any(), (step, o, "level S+2 of a uint8 build is +0 outside the support",
+                                                    int(np.count_nonzero(top[outside])))
+                    assert not (top & 0x80000000).any(), (step, o, "a uint8 build left a sign bit in level S+2")
+                else:
+                    assert (w == 0x80000000).mean() > 0.5  # the image does what the test needs: mostly -0
+                    _assert_same(top, w, (step, o, "the oracle's signs"))
+            _check_levels(ctx, 0, want, S, O, ("format", kern, step))
+
+
+# the smallest shapes: one group, one tile column of one group, a second tile column of one group
+# (17 x 260: every lane but one clamped and masked), less than one tile row
+SMALL = {"1x4": (1, 4), "16x4": (16, 4), "17x260": (17, 260), "15x512": (15, 512)}
+
+
+@pytest.mark.parametrize("octaves", [0, 1, 2, 3, 4])
+@pytest.mark.parametrize("kern", KERNELS)
+@pytest.mark.parametrize("shape", sorted(SMALL))
+def test_smallest_shapes_with_every_octave_count(pkg, oracle, shape, kern, octaves):
+    """Octaves forced to 1..4 (kp_F < 5: oct[o] beyond O holds no rows) and the default; an octave
+    count the shape does not have is refused at creation."""
+    H, W = SMALL[shape]
+    S = 2
+    if octaves > oracle.default_octaves(H, W):
+        with pytest.raises(pkg.GdpError):
+            pkg.PyramidContext(H, W, S=S, octaves=octaves)
+        return
+    O = octaves or oracle.default_octaves(H, W)
+    a, b = _images(oracle, H, W, 31 + H)
+    c = -b
+    with pkg.PyramidContext(H, W, S=S, octaves=octaves) as ctx:
+        assert ctx.O == O
+        ctx.set_tuning(keep_kernel=kern)
+        for k, img in enumerate((a, b, c)):
+            ctx.set_input(img)
+            assert ctx.tuning()["zeros_clean"] == min(k, 1)
+            ctx.build()
+            ctx.sync()
+            _check_levels(ctx, 0, _want_levels(oracle, ctx, img, H, W, S, O), S, O, (shape, kern, octaves, k))

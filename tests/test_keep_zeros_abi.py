@@ -23,7 +23,7 @@ READ_ONLY = {
     "gdp_download_level", "gdp_download_level_rows", "gdp_download_pyramid_rows", "gdp_download_level_range",
     "gdp_download_pyramid", "gdp_download_image_raw", "gdp_host_defer", "gdp_get_taps", "gdp_checksum",
     "gdp_set_keypoint_capacity", "gdp_detect_extrema", "gdp_keypoint_count", "gdp_download_keypoints", "gdp_sync",
-    "gdp_set_tuning",
+    "gdp_set_tuning", "gdp_refine_keypoints", "gdp_refined_count", "gdp_download_refined", "gdp_upload_keypoints",
 }
 BUILDERS = {"gdp_build", "gdp_autotune", "gdp_time_builds"}
 
