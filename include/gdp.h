@@ -561,7 +561,28 @@ enum {
                                    by a gdp_build into the context-owned pyramid, cleared by every
                                    call that writes, moves or rebinds pyramid memory and by
                                    gdp_pyramid_written) */
-    GDP_TUNE_KEEP_KERNEL = 23   /* the kernel of a gdp_build that skips those stores (the steady
+    GDP_TUNE_KEEP_SIGNS = 24,   /* 1 (default): a steady-state build by k_keep (GDP_TUNE_KEEP_KERNEL
+                                   >= 1) on int32 input does not store level S+2 = copysign(0, x)
+                                   again where it would store +0 over +0: the context keeps a sign
+                                   map on the device, one byte per input row of a 16 x 256 tile,
+                                   and a row with no negative pixel now and none at the build
+                                   before stores nothing.  The first such build after anything that
+                                   clears GDP_TUNE_ZEROS_CLEAN, or after any other kind of build,
+                                   stores everything and writes the map; the saving starts with the
+                                   second.  A build that skips by the map runs k_keep with 4 rows
+                                   per wave at every size (it barely stores; read-only
+                                   GDP_TUNE_KEEP_SIGNS_KERNEL), unless GDP_TUNE_KEEP_KERNEL was set
+                                   by the caller; the build that writes the map makes every store
+                                   and keeps GDP_TUNE_KEEP_KERNEL's shape.  uint8 input stores as before.  The same bits
+                                   either way; 0 = every steady-state build stores all of level
+                                   S+2.  A launch-time flag: no drain */
+    GDP_TUNE_SIGNS_KNOWN = 25,  /* read-only: 1 while the sign map describes the context's pyramid
+                                   (set by an int32 k_keep build with GDP_TUNE_KEEP_SIGNS = 1,
+                                   cleared by whatever clears GDP_TUNE_ZEROS_CLEAN, by every other
+                                   build and by a switch of GDP_TUNE_KEEP_SIGNS) */
+    GDP_TUNE_KEEP_SIGNS_KERNEL = 26, /* read-only: the k_keep shape (a GDP_TUNE_KEEP_KERNEL value) of a
+                                   build that skips by the sign map; 0 while GDP_TUNE_KEEP_KERNEL is 0 */
+    GDP_TUNE_KEEP_KERNEL = 23  /* the kernel of a gdp_build that skips those stores (the steady
                                    state): 0 = the build kernel's own keep path; 1, 2 = the
                                    steady-state kernel k_keep — one pass over the input on
                                    16 x 256 tiles, level S+2 of every fused octave stored from the
@@ -592,9 +613,10 @@ void* gdp_stream(const gdp_ctx* ctx);          /* the context's own hipStream_t 
 const char* gdp_last_error(const gdp_ctx* ctx); /* ctx may be NULL: last create() failure */
 const char* gdp_status_string(int status);
 /* Time `iters` back-to-back gdp_build launches on `stream` with HIP events recorded on that same
- * stream; writes the total milliseconds.  Used by bench.py for the per-launch kernel time.  One
- * untimed build runs first, so every timed launch finds the pyramid in the same state (clean, with
- * GDP_TUNE_KEEP_ZEROS: the steady state of a context that is built again and again; the cost of a
+ * stream; writes the total milliseconds.  Used by bench.py for the per-launch kernel time.  Two
+ * untimed builds run first, so every timed launch finds the pyramid in the same state (clean, with
+ * GDP_TUNE_KEEP_ZEROS, after the first; the sign map known, with GDP_TUNE_KEEP_SIGNS, after the
+ * second: the steady state of a context that is built again and again; the cost of a
  * first build is what GDP_TUNE_KEEP_ZEROS = 0 times).  gdp_autotune times its candidates this way. */
 int gdp_time_builds(gdp_ctx* ctx, int iters, void* stream, float* total_ms);
 

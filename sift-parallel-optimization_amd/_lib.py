@@ -33,6 +33,9 @@ GDP_TUNE_PYRAMID_CHUNK_KB = 20
 GDP_TUNE_KEEP_ZEROS = 21
 GDP_TUNE_ZEROS_CLEAN = 22
 GDP_TUNE_KEEP_KERNEL = 23
+GDP_TUNE_KEEP_SIGNS = 24
+GDP_TUNE_SIGNS_KNOWN = 25
+GDP_TUNE_KEEP_SIGNS_KERNEL = 26
 
 
 class GdpError(RuntimeError):

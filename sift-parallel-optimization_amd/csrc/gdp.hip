@@ -154,6 +154,17 @@ struct gdp_ctx {
     int keep_zeros = 1;           // GDP_TUNE_KEEP_ZEROS: 0 = every build stores every byte
     int keep_kernel = 1;          // GDP_TUNE_KEEP_KERNEL: 0 = a kept build runs k_build's keep path, >= 1 = k_keep
                                   // (kKeepKernels) where the context is eligible (launch_build); default by size
+    // k_keep's sign map (gdp_keep.inc): [batch][kp_tiles_per_img][kTileRows] bytes, allocated with the
+    // context.  signs_known: the map describes the context's pyramid — set by an int32 k_keep launch
+    // with keep_signs on (the only code that writes the map), cleared wherever zeros_clean is cleared
+    // and by every other build.  While set, the next such launch skips the rows whose level-S+2 words
+    // already hold the +0 it would store.  Changed at enqueue time on the host, like zeros_clean.
+    unsigned char* d_signs = nullptr;
+    bool signs_known = false;
+    int keep_signs = 1;           // GDP_TUNE_KEEP_SIGNS: 0 = every steady-state build stores all of level S+2
+    int keep_kernel_signs = 1;    // GDP_TUNE_KEEP_SIGNS_KERNEL: the k_keep shape (kKeepKernels id) of a launch that skips by
+                                  // the map (kSignsUse), where keep_kernel >= 1 takes k_keep at all: its own default by
+                                  // measurement; GDP_TUNE_KEEP_KERNEL sets both
     long long img_floats = 0;     // one image's dense extent (pyr_stride may be larger: GDP_IMAGE_STRIDE_MB)
     // GDP_SPREAD_VMM: the pyramid as one reserved address range with separately created physical
     // chunks mapped into it (alloc_spread); each entry: handle, byte offset, bytes
@@ -281,8 +292,10 @@ int upload_geom(gdp_ctx* c) {
 
 // Every writer of pyramid memory (and everything that moves or rebinds it) passes through here:
 // the next build stores every byte again.
+inline void signs_unknown(gdp_ctx* c) { c->signs_known = false; }
 inline void pyramid_written(gdp_ctx* c) {
     if (c) c->zeros_clean = false;
+    if (c) signs_unknown(c);
 }
 // First statement of every export that takes a non-const context: GDP_WRITES_PYRAMID unless the
 // export provably leaves the context's pyramid alone (GDP_READS_PYRAMID — the explicit read-only
@@ -299,6 +312,9 @@ int launch_build(gdp_ctx* c, hipStream_t st, bool subset = false) {
     const bool own = c->d_out == c->d_out_own;
     const int keep = (!subset && c->keep_zeros && c->zeros_clean && own) ? 1 : 0;
     c->zeros_clean = false;
+    // the sign map likewise: only an int32 k_keep launch below leaves it known
+    const bool signs = c->signs_known;
+    signs_unknown(c);
     if (units == 0) return GDP_OK;
     // default: one unit per block; GDP_TUNE_GRID / GDP_TUNE_BLOCKS_PER_CU cap it (persistent loop)
     const long long cap = c->grid_override > 0 ? c->grid_override : (c->persistent ? c->blocks_max : units);
@@ -308,11 +324,19 @@ int launch_build(gdp_ctx* c, hipStream_t st, bool subset = false) {
         // loads everywhere; any other context keeps k_build's keep path below.  Its units are the
         // Geom's kp_* fields, whatever variant is selected; a launch-time choice like `keep` itself.
         const long long kunits = (long long)g.kp_tiles_total + g.kp_tail_units;
-        const KeepKernel& kk = kKeepKernels[c->keep_kernel - 1];
-        hipLaunchKernelGGL(kk.k[c->nontemporal ? 1 : 0], dim3((unsigned)std::min<long long>(kunits, cap)), dim3(kk.block), 0,
-                           st, c->d_geom, c->d_in, c->d_out, c->d_taps);
+        // The sign map (GDP_TUNE_KEEP_SIGNS): int32 input only (a uint8 launch stores +0 without
+        // reading and leaves the map stale).  The first launch after anything that invalidated the
+        // map stores everything and writes it; the ones after skip the rows that owe nothing.
+        const int mode = (c->keep_signs && g.in_fmt != GDP_INPUT_U8) ? (signs ? kSignsUse : kSignsEstablish) : kSignsOff;
+        // The shape: a launch that makes every store (kSignsOff, and the establishing launch: the map is per row,
+        // whatever the rows per wave) keeps GDP_TUNE_KEEP_KERNEL's; only the skipping launch takes its own default.
+        const KeepKernel& kk = kKeepKernels[(mode == kSignsUse ? c->keep_kernel_signs : c->keep_kernel) - 1];
+        // (kSignsOff launches the instantiation without the map's code: the kernel as it was before the map)
+        hipLaunchKernelGGL(kk.k[mode != kSignsOff][c->nontemporal ? 1 : 0], dim3((unsigned)std::min<long long>(kunits, cap)),
+                           dim3(kk.block), 0, st, c->d_geom, c->d_in, c->d_out, c->d_taps, c->d_signs, mode);
         GDP_HIP(c, hipGetLastError());
         c->zeros_clean = true;  // keep != 0: a full build into the context's own pyramid
+        c->signs_known = mode != kSignsOff;
         return GDP_OK;
     }
     const BuildVariant& v = kVariants[variant_index(c->variant)];
@@ -773,6 +797,7 @@ static void free_pyramid(gdp_ctx* c) {
     c->d_out_own = nullptr;
     c->pyr_chunk_kb = 0;
     c->zeros_clean = false;  // whatever backs the pyramid next holds nothing yet
+    signs_unknown(c);
 }
 
 // The pyramid's default backing (GDP_SPREAD_VMM=0 opts out): reserve its address range
@@ -959,7 +984,7 @@ int gdp_create_band(gdp_ctx** out, int H, int W, int S, int O, int batch, int ro
     // profiles/ab_sub_c*_r03m.log), 256-thread blocks on small batches, 1024-thread above
     c->inplace_sub = batch == 1 ? 16 : (long long)(row_end - row_begin) * W * batch <= (32ll << 20) ? 4 : 1;
     // Steady-state build (k_keep, GDP_TUNE_KEEP_KERNEL), by pixels per launch — measured on the rotated cold
-    // sets bench.py times (profiles/keep_kernel_shapes_r08.json; ms for kernel 0 / 1 / 2):
+    // sets bench.py times, every level-S+2 store made (profiles/keep_kernel_shapes_r08.json; ms for kernel 0 / 1 / 2):
     //   under 8 Mpix the launch is all ramp and drain and k_build's 16-wave blocks win: 2048^2 0.0145 / 0.0219 /
     //   0.0156 -> 0;
     //   up to 64 Mpix 8-wave blocks, 2 rows per wave — more, shorter waves: 4096^2 0.0421 / 0.0381 / 0.0294,
@@ -969,6 +994,19 @@ int gdp_create_band(gdp_ctx** out, int H, int W, int S, int O, int batch, int ro
     //   64 x 4096^2 2.450 / 1.582 / 1.601, 16384^2 0.598 / 0.393 / 0.391 -> 1.
     const long long kp_px = (long long)(row_end - row_begin) * W * batch;
     c->keep_kernel = kp_px < (1ll << 23) ? 0 : kp_px <= (1ll << 26) ? 2 : 1;
+    // A launch that skips by the sign map (GDP_TUNE_KEEP_SIGNS, int32 input, the map known) stores next to nothing on non-negative
+    // input, and with no stores to spread over more, shorter waves the 4 rows in flight per wave win wherever k_keep
+    // runs at all (profiles/keep_signs_shapes_r11.json; k_build's keep path cannot skip the stores, so 0 stays 0):
+    //   8 x 1080x1920 0.0432 / 0.0344 / 0.0389, 4096^2 0.0422 / 0.02385 / 0.02383 (a tie), 8192 x 4096 0.0790 / 0.0306 /
+    //   0.0417, 4 x 4096^2 0.158 / 0.0599 / 0.0855, 64 x 1080x1920 0.315 / 0.182 / 0.261, 16384^2 0.597 / 0.164 /
+    //   0.285, 64 x 4096^2 2.44 / 0.774 / 1.31 -> 1.  (2048^2: 0.0140 / 0.0188 / 0.0129; one shape under 8 Mpix is
+    //   not enough to move that threshold.)  Launches that make the stores (uint8 input, GDP_TUNE_KEEP_SIGNS = 0,
+    //   the launch that establishes the map) keep the choice above; a caller's GDP_TUNE_KEEP_KERNEL sets both.
+    //   An image with negative pixels everywhere makes every store in a skipping launch too, and pays for the shape
+    //   that is wrong for stores (all-negative 4096^2: 0.0400 ms on shape 1, 0.0362 on shape 2, the parent 0.0333):
+    //   up to 16 Mpix, where the two shapes tie on non-negative 4096^2, the store-making choice stays (at the cost of
+    //   8 x 1080x1920's 0.0389 instead of 0.0344 ms).
+    c->keep_kernel_signs = (c->keep_kernel > 0 && kp_px <= (1ll << 24)) ? c->keep_kernel : 1;
     // Convolution extension default: block tiles (16 waves) in block order 5 (below; octave-o block
     // rows right after the octave-0 rows that hold their input rows, XCD-chunked) — the fastest form
     // on every config (tools/conv_ab.sh, cold buffers: 4096^2 0.111 ms vs 0.119 for the sweep,
@@ -1175,6 +1213,13 @@ int gdp_create_band(gdp_ctx** out, int H, int W, int S, int O, int batch, int ro
     }
     c->d_out = c->d_out_own;
     c->zeros_clean = false;  // fresh memory: the first build stores every byte
+    signs_unknown(c);
+    {
+        // k_keep's sign map; zeroed so the bytes of rows beyond the image, which no launch writes, are defined
+        const size_t nb = std::max<size_t>(16, (size_t)g.kp_tiles_total * kTileRows);
+        if ((e = hipMalloc(&c->d_signs, nb)) != hipSuccess) return hip_fail(e, "hipMalloc(sign map)");
+        if ((e = hipMemset(c->d_signs, 0, nb)) != hipSuccess) return hip_fail(e, "hipMemset(sign map)");
+    }
     if ((e = hipMalloc(&c->d_sum, sizeof(unsigned long long))) != hipSuccess) return hip_fail(e, "hipMalloc(sum)");
     c->d_in = c->d_in_own;
     if ((e = hipMemcpy(c->d_taps, c->h_taps.data(), c->h_taps.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
@@ -1224,6 +1269,7 @@ void gdp_destroy(gdp_ctx* c) {
     if (c->st_up) (void)hipStreamDestroy(c->st_up);
     if (c->st_down) (void)hipStreamDestroy(c->st_down);
     if (c->d_sum) (void)hipFree(c->d_sum);
+    if (c->d_signs) (void)hipFree(c->d_signs);
     if (c->d_kp) (void)hipFree(c->d_kp);
     if (c->d_kp_count) (void)hipFree(c->d_kp_count);
     if (c->d_rf) (void)hipFree(c->d_rf);
@@ -2601,6 +2647,9 @@ static int ensure_keypoints(gdp_ctx* c) {
     if (e == hipSuccess && !c->d_kp_count) {
         e = hipMalloc(reinterpret_cast<void**>(&c->d_kp_count), batch * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMemset(c->d_kp_count, 0, batch * sizeof(uint32_t));
+        // hipMemset runs on the null stream, which the context's non-blocking stream does not wait for: it must
+        // have landed before a launch on that stream counts into the buffer
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     }
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -2621,6 +2670,9 @@ static int ensure_refined(gdp_ctx* c) {
     if (e == hipSuccess && !c->d_rf_count) {
         e = hipMalloc(reinterpret_cast<void**>(&c->d_rf_count), batch * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMemset(c->d_rf_count, 0, batch * sizeof(uint32_t));
+        // hipMemset runs on the null stream, which the context's non-blocking stream does not wait for: it must
+        // have landed before a launch on that stream counts into the buffer
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     }
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -3013,6 +3065,9 @@ int gdp_get_tuning(const gdp_ctx* c, int key, int* value) try {
         case GDP_TUNE_KEEP_ZEROS: *value = c->keep_zeros; return GDP_OK;
         case GDP_TUNE_ZEROS_CLEAN: *value = c->zeros_clean ? 1 : 0; return GDP_OK;
         case GDP_TUNE_KEEP_KERNEL: *value = c->keep_kernel; return GDP_OK;
+        case GDP_TUNE_KEEP_SIGNS: *value = c->keep_signs; return GDP_OK;
+        case GDP_TUNE_SIGNS_KNOWN: *value = c->signs_known ? 1 : 0; return GDP_OK;
+        case GDP_TUNE_KEEP_SIGNS_KERNEL: *value = c->keep_kernel > 0 ? c->keep_kernel_signs : 0; return GDP_OK;
         default: return GDP_ERR_ARG;
     }
 } GDP_ABI_CATCH(c)
@@ -3090,9 +3145,21 @@ int gdp_set_tuning(gdp_ctx* c, int key, int value) try {
             if (value < 0 || value > kNumKeepKernels)
                 return c->status(GDP_ERR_ARG, "keep kernel must be 0 (k_build's keep path) or 1..%d (k_keep)", kNumKeepKernels);
             c->keep_kernel = value;  // a launch-time decision like GDP_TUNE_KEEP_ZEROS: no geometry upload, no drain
+            if (value > 0) c->keep_kernel_signs = value;
             return GDP_OK;
         case GDP_TUNE_ZEROS_CLEAN:
             return c->status(GDP_ERR_ARG, "GDP_TUNE_ZEROS_CLEAN is read-only (gdp_pyramid_written clears it)");
+        case GDP_TUNE_KEEP_SIGNS:
+            if (value != 0 && value != 1) return c->status(GDP_ERR_ARG, "keep signs must be 0 or 1");
+            // a launch-time decision (a kernel argument): no geometry upload, no drain.  Launches with
+            // the knob off do not keep the map, so a switch either way leaves it unknown.
+            if (value != c->keep_signs) signs_unknown(c);
+            c->keep_signs = value;
+            return GDP_OK;
+        case GDP_TUNE_KEEP_SIGNS_KERNEL:
+            return c->status(GDP_ERR_ARG, "GDP_TUNE_KEEP_SIGNS_KERNEL is read-only (GDP_TUNE_KEEP_KERNEL sets it)");
+        case GDP_TUNE_SIGNS_KNOWN:
+            return c->status(GDP_ERR_ARG, "GDP_TUNE_SIGNS_KNOWN is read-only (what clears GDP_TUNE_ZEROS_CLEAN clears it)");
         case GDP_TUNE_CONV_ORDER:
             if (value < 0 || value > 7) return c->status(GDP_ERR_ARG, "conv order must be 0..7");
             c->conv_order = value;
@@ -3139,9 +3206,11 @@ int gdp_time_builds(gdp_ctx* c, int iters, void* stream, float* total_ms) try {
     hipEvent_t e0, e1;
     GDP_HIP(c, hipEventCreate(&e0));
     GDP_HIP(c, hipEventCreate(&e1));
-    // one untimed build first: every timed launch then runs in the same (clean, GDP_TUNE_KEEP_ZEROS)
-    // state, whatever the caller did to the pyramid before
+    // two untimed builds first: every timed launch then runs in the same state — clean
+    // (GDP_TUNE_KEEP_ZEROS) after the first, the sign map known (GDP_TUNE_KEEP_SIGNS) after the
+    // second — whatever the caller did to the pyramid before
     int rc = launch_build(c, st);
+    if (rc == GDP_OK) rc = launch_build(c, st);
     if (rc == GDP_OK && hipEventRecord(e0, st) != hipSuccess) rc = c->status(GDP_ERR_HIP, "hipEventRecord");
     for (int i = 0; i < iters && rc == GDP_OK; ++i) rc = launch_build(c, st);
     if (rc == GDP_OK && hipEventRecord(e1, st) != hipSuccess) rc = c->status(GDP_ERR_HIP, "hipEventRecord");

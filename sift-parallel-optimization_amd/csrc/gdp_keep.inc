@@ -11,6 +11,18 @@
 // k_build's keep path does the same work one 4-pixel group per thread, reading the input again for
 // octaves 1-4 (DESIGN §10); it stays as the fallback (contexts this kernel does not take) and as
 // GDP_TUNE_KEEP_KERNEL = 0.
+//
+// The sign map (GDP_TUNE_KEEP_SIGNS, gdp_ctx::d_signs): pixel intensities are non-negative, so on
+// real input every one of those stores writes +0 over the +0 the build before left there.  The
+// context keeps one byte per (image, tile, tile row) — [batch][kp_tiles_per_img][kTileRows] — that
+// only this kernel's int32 register stores maintain.  While the host holds the map valid
+// (gdp_ctx::signs_known), byte = 0 means: every level-S+2 word keep_tile_fast stores from that
+// input row within the tile's 256 columns holds +0 in the context's pyramid, in every fused octave
+// (octave o stores from rows = 0 mod 2^o only; the set of fast (tile, octave) pairs is fixed per
+// context, OctGeom::sp_*).  A row whose byte is 0 and whose 256 pixels are all non-negative owes
+// no store at all.  `signs`: kSignsOff — store everything, never touch the map; kSignsEstablish —
+// store everything and write every row's byte; kSignsUse — skip such rows, keep the bytes current.
+enum { kSignsOff = 0, kSignsEstablish = 1, kSignsUse = 2 };
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -58,18 +70,40 @@ __device__ __forceinline__ void keep_tail_unit(const Geom* __restrict__ g, const
 // divergent load) and masked for the stores.  I32 = false (uint8 input): a pixel has no sign, so
 // level S+2 is +0 and nothing is read.  `fast` bit o: store octave o; row[o] / cols[o] / off[o]:
 // rows held, columns and float offset of level (o, S+2) in the image's pyramid (0 rows beyond O).
-template <bool NT, int RPL, bool I32>
+// `flags`: the tile's kTileRows bytes of the sign map (I32 and signs != kSignsOff only).  A row's
+// byte is the wave-wide OR of the sign bits of the 256 pixels the wave loaded for it (lanes clamped
+// for the load hold copies of valid pixels of the same tile row or column range: harmless); the
+// wave's RPL bytes are contiguous and RPL-aligned, read with one load issued with the pixels'.
+// Every branch on them is wave-uniform.  A byte is written by lane 0 alone, never for a row beyond
+// the image, and under kSignsUse only when it changes.  Establishing, the stores run first, each
+// row's as soon as its pixels are there, and the flags are written after them.  Using the map, all
+// rows' decisions are taken before the first store: a wave none of whose rows owes a store ends
+// there, one whose rows all do runs the same straight-line stores as without the map.  SIGNS = false (kSignsOff, and uint8 input) compiles
+// none of this: the kernel as it was before the map, at its speed.
+template <bool NT, int RPL, bool I32, bool SIGNS>
 __device__ __forceinline__ void keep_tile_fast(const Geom* __restrict__ g, const void* __restrict__ in,
                                                float* __restrict__ img_out, unsigned b, int in_r0, int in_c0, unsigned fast,
                                                const int (&rows)[kFused], const int (&cols)[kFused],
-                                               const long long (&off)[kFused]) {
+                                               const long long (&off)[kFused], unsigned char* flags, int signs) {
+    static_assert(RPL == 2 || RPL == 4, "one aligned load of a wave's flags");
+    static_assert(I32 || !SIGNS, "uint8 input has no sign: it never uses the map");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = in_c0 + 4 * lane;
     const int rt0 = wave * RPL;  // first tile row of this wave
     const int in_rows = g->in_rows, W = g->W;
     const bool col_ok = c < W;
     i4 x[RPL];
+    unsigned old = 0;  // byte j: the flag of row rt0 + j as the build before left it
     if constexpr (I32) {
+        if constexpr (SIGNS) {
+            if (signs == kSignsUse) {
+                if constexpr (RPL == 4)
+                    old = *reinterpret_cast<const unsigned*>(flags + rt0);
+                else
+                    old = *reinterpret_cast<const unsigned short*>(flags + rt0);
+                old = (unsigned)__builtin_amdgcn_readfirstlane((int)old);
+            }
+        }
         const int* src = static_cast<const int*>(in) + (long long)b * g->in_img_stride + min(c, W - 4);
         const long long pitch = g->in_pitch;
 #pragma unroll
@@ -79,10 +113,29 @@ __device__ __forceinline__ void keep_tile_fast(const Geom* __restrict__ g, const
 #pragma unroll
         for (int j = 0; j < RPL; ++j) x[j] = i4{0, 0, 0, 0};
     }
+    if constexpr (!SIGNS) {
+        // the kernel as it was before the map, statement for statement (regrouped into the helper
+        // below it ran uint8 input 2 % slower)
 #pragma unroll
-    for (int j = 0; j < RPL; ++j) {
-        const int rr = in_r0 + rt0 + j;  // band-local input row
-        const int rt = rt0 + j;          // row of the tile: rt % 2^o == 0 <=> rr % 2^o == 0 (in_r0 % 16 == 0)
+        for (int j = 0; j < RPL; ++j) {
+            const int rr = in_r0 + rt0 + j;  // band-local input row
+            const int rt = rt0 + j;          // row of the tile: rt % 2^o == 0 <=> rr % 2^o == 0 (in_r0 % 16 == 0)
+            const f4 s = __builtin_bit_cast(f4, x[j] & (int)0x80000000u);
+            if ((fast & 1u) && col_ok && rr < rows[0]) st_f4<NT>(img_out + off[0] + (long long)rr * cols[0] + c, s);
+            if ((fast & 2u) && (rt & 1) == 0 && (rr >> 1) < rows[1] && (c >> 1) < cols[1])
+                st_f2<NT>(img_out + off[1] + (long long)(rr >> 1) * cols[1] + (c >> 1), f2{s.x, s.z});
+            if ((fast & 4u) && (rt & 3) == 0 && (rr >> 2) < rows[2] && (c >> 2) < cols[2])
+                st_f1<NT>(img_out + off[2] + (long long)(rr >> 2) * cols[2] + (c >> 2), s.x);
+            if ((fast & 8u) && (rt & 7) == 0 && (lane & 1) == 0 && (rr >> 3) < rows[3] && (c >> 3) < cols[3])
+                st_f1<NT>(img_out + off[3] + (long long)(rr >> 3) * cols[3] + (c >> 3), s.x);
+            if ((fast & 16u) && (rt & 15) == 0 && (lane & 3) == 0 && (rr >> 4) < rows[4] && (c >> 4) < cols[4])
+                st_f1<NT>(img_out + off[4] + (long long)(rr >> 4) * cols[4] + (c >> 4), s.x);
+        }
+        return;
+    }
+    auto store_row = [&](int j) {
+        const int rr = in_r0 + rt0 + j;
+        const int rt = rt0 + j;
         const f4 s = __builtin_bit_cast(f4, x[j] & (int)0x80000000u);
         if ((fast & 1u) && col_ok && rr < rows[0]) st_f4<NT>(img_out + off[0] + (long long)rr * cols[0] + c, s);
         if ((fast & 2u) && (rt & 1) == 0 && (rr >> 1) < rows[1] && (c >> 1) < cols[1])
@@ -93,7 +146,41 @@ __device__ __forceinline__ void keep_tile_fast(const Geom* __restrict__ g, const
             st_f1<NT>(img_out + off[3] + (long long)(rr >> 3) * cols[3] + (c >> 3), s.x);
         if ((fast & 16u) && (rt & 15) == 0 && (lane & 3) == 0 && (rr >> 4) < rows[4] && (c >> 4) < cols[4])
             st_f1<NT>(img_out + off[4] + (long long)(rr >> 4) * cols[4] + (c >> 4), s.x);
+    };
+    auto negative = [&](int j) -> unsigned {  // wave-uniform: some pixel of the row's 256 is negative
+        return __ballot((x[j].x | x[j].y | x[j].z | x[j].w) < 0) != 0 ? 1u : 0u;
+    };
+    if (signs != kSignsUse) {
+        // establishing: every store as ever, each row's as soon as its pixels are there; the flags after them
+#pragma unroll
+        for (int j = 0; j < RPL; ++j) store_row(j);
+#pragma unroll
+        for (int j = 0; j < RPL; ++j) {
+            const unsigned neg = negative(j);
+            if (lane == 0 && in_r0 + rt0 + j < in_rows) flags[rt0 + j] = (unsigned char)neg;
+        }
+        return;
     }
+    // bit j of `run`: row rt0 + j runs its stores iff its flag is set (the build before left a -0
+    // there) or a pixel of it is negative now
+    constexpr unsigned kAll = (1u << RPL) - 1u;
+    unsigned run = 0u;
+#pragma unroll
+    for (int j = 0; j < RPL; ++j) {
+        const unsigned neg = negative(j);
+        const unsigned was = (old >> (8 * j)) & 0xffu;
+        if (was != neg && lane == 0 && in_r0 + rt0 + j < in_rows) flags[rt0 + j] = (unsigned char)neg;
+        run |= ((was | neg) ? 1u : 0u) << j;
+    }
+    if (run == 0) return;  // +0 over +0 in every row of the wave: nothing owed
+    if (run != kAll) {
+#pragma unroll
+        for (int j = 0; j < RPL; ++j)
+            if (run >> j & 1u) store_row(j);
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < RPL; ++j) store_row(j);
 }
 
 // Work units: [0, kp_tiles_total) are kTileRows x kTileCols input tiles, [kp_tiles_total,
@@ -103,9 +190,10 @@ __device__ __forceinline__ void keep_tile_fast(const Geom* __restrict__ g, const
 // store aligned.  Per (tile, octave), wave-uniformly: the octave's footprint of the tile misses the
 // support (OctGeom::sp_*) -> the register stores above; else that octave's groups of the tile go
 // through build_group's keep path, which tests each group and is exact by construction.
-template <bool NT, int RPL>
+template <bool NT, int RPL, bool SIGNS>
 __global__ void __launch_bounds__(64 * kTileRows / RPL) k_keep(const Geom* __restrict__ g, const void* __restrict__ in,
-                                                               float* __restrict__ out, const float* __restrict__ taps) {
+                                                               float* __restrict__ out, const float* __restrict__ taps,
+                                                               unsigned char* sign_map, int signs) {
     constexpr int BLK = 64 * kTileRows / RPL;
     static_assert(kTileCols == 256 && kTileRows == 16 && kFused == 5 && kTileRows % RPL == 0, "k_keep's tile");
     const unsigned tiles_total = g->kp_tiles_total;
@@ -148,10 +236,13 @@ __global__ void __launch_bounds__(64 * kTileRows / RPL) k_keep(const Geom* __res
         }
         if (fast) {
             float* img_out = out + (long long)b * g->pyr_stride;
+            // the tile's bytes of the sign map, by its position in the image (not by its place in the order)
+            unsigned char* flags =
+                sign_map + ((size_t)b * g->kp_tiles_per_img + tr * (unsigned)g->kp_tiles_c + tc) * (size_t)kTileRows;
             if (g->in_fmt == GDP_INPUT_U8)
-                keep_tile_fast<NT, RPL, false>(g, in, img_out, b, in_r0, in_c0, fast, rows, cols, off);
+                keep_tile_fast<NT, RPL, false, false>(g, in, img_out, b, in_r0, in_c0, fast, rows, cols, off, flags, kSignsOff);
             else
-                keep_tile_fast<NT, RPL, true>(g, in, img_out, b, in_r0, in_c0, fast, rows, cols, off);
+                keep_tile_fast<NT, RPL, true, SIGNS>(g, in, img_out, b, in_r0, in_c0, fast, rows, cols, off, flags, signs);
         }
         const unsigned slow = ~fast & ((1u << F) - 1u);
         if (!slow) continue;
@@ -182,10 +273,14 @@ __global__ void __launch_bounds__(64 * kTileRows / RPL) k_keep(const Geom* __res
 // GDP_TUNE_KEEP_KERNEL values >= 1: rows per lane (block = 16 / rows waves); all bit-identical.
 struct KeepKernel {
     int id, block;
-    void (*k[2])(const Geom*, const void*, float*, const float*); // [NT]
+    void (*k[2][2])(const Geom*, const void*, float*, const float*, unsigned char*, int); // [uses the sign map][NT]
 };
-#define GDP_KEEP_KERNEL(ID, RPL) \
-    KeepKernel { ID, 64 * kTileRows / RPL, {k_keep<false, RPL>, k_keep<true, RPL>} }
+#define GDP_KEEP_KERNEL(ID, RPL)                                                      \
+    KeepKernel {                                                                      \
+        ID, 64 * kTileRows / RPL, {                                                   \
+            {k_keep<false, RPL, false>, k_keep<true, RPL, false>}, {k_keep<false, RPL, true>, k_keep<true, RPL, true>} \
+        }                                                                             \
+    }
 const KeepKernel kKeepKernels[] = {
     GDP_KEEP_KERNEL(1, 4), // 4 waves, 4 rows (4 KiB of loads) per wave
     GDP_KEEP_KERNEL(2, 2), // 8 waves, 2 rows per wave

@@ -296,8 +296,8 @@ class PyramidContext:
 
     _TUNING = ("nontemporal", "blocks_per_cu", "grid", "variant", "tile_order", "inplace_sub", "window_sub",
                "conv_kernel", "conv_rows", "conv_order", "build_lds", "stage_kb", "stage_threads", "conv_waves", "zero_window",
-               "store_pace", "conv_pace", "inplace_pace", "keep_zeros", "keep_kernel",
-               "pyramid_chunk_kb", "zeros_clean")  # the last two read-only
+               "store_pace", "conv_pace", "inplace_pace", "keep_zeros", "keep_kernel", "keep_signs",
+               "pyramid_chunk_kb", "zeros_clean", "signs_known", "keep_signs_kernel")  # the last four read-only
 
     @staticmethod
     def _tuning_key(name):
@@ -309,7 +309,7 @@ class PyramidContext:
                    inplace_sub=None, window_sub=None, conv_kernel=None, conv_rows=None, conv_order=None,
                    build_lds=None, stage_kb=None, stage_threads=None, conv_waves=None, zero_window=None,
                    store_pace=None, conv_pace=None, inplace_pace=None, keep_zeros=None,
-                   keep_kernel=None):
+                   keep_kernel=None, keep_signs=None):
         """Performance knobs of the kernels (outputs are bit-identical for every setting; the
         conv_* knobs select the convolution extension's kernel: 0 register sweep, 1 LDS tiles,
         2 block tiles, and the sweep's rows per wave strip (16 / 32) or the block tiles' rows per
@@ -323,13 +323,16 @@ class PyramidContext:
         zeros outside the windows' support that the previous build of this context already stored —
         tuning()["zeros_clean"] tells whether the next build may leave them; keep_kernel picks the
         kernel of such a build: 0 the build kernel's own keep path, 1 / 2 the steady-state kernel with
-        4 / 2 rows per wave, taken where the width is a multiple of 4)."""
+        4 / 2 rows per wave, taken where the width is a multiple of 4; keep_signs = 0 makes every
+        such build store all of level S+2 = copysign(0, x), instead of skipping the tile rows that
+        held no negative int32 pixel at this build and the one before —
+        tuning()["signs_known"] tells whether the next one may skip)."""
         vals = dict(nontemporal=nontemporal, blocks_per_cu=blocks_per_cu, grid=grid, variant=variant,
                     tile_order=tile_order, inplace_sub=inplace_sub, window_sub=window_sub, conv_kernel=conv_kernel,
                     conv_rows=conv_rows, conv_order=conv_order, build_lds=build_lds, stage_kb=stage_kb,
                     stage_threads=stage_threads, conv_waves=conv_waves, zero_window=zero_window,
                     store_pace=store_pace, conv_pace=conv_pace, inplace_pace=inplace_pace, keep_zeros=keep_zeros,
-                    keep_kernel=keep_kernel)
+                    keep_kernel=keep_kernel, keep_signs=keep_signs)
         for name, val in vals.items():
             if val is not None:
                 check(lib().gdp_set_tuning(self._ctx, self._tuning_key(name), int(val)), self._ctx)

@@ -42,7 +42,9 @@ def run(args):
         # the classic records count a build that stores every byte (keep_zeros = 0, the first build
         # of a context); --keep-zeros 1 counts the steady state (every set built once before)
         # --keep-kernel: the kernel of those steady-state builds (GDP_TUNE_KEEP_KERNEL; default: the library's)
-        c.set_tuning(zero_window=args.zero_window, keep_zeros=args.keep_zeros, keep_kernel=args.keep_kernel)
+        # --keep-signs: whether k_keep skips the level-S+2 stores of rows with no negative pixel (GDP_TUNE_KEEP_SIGNS)
+        c.set_tuning(zero_window=args.zero_window, keep_zeros=args.keep_zeros, keep_kernel=args.keep_kernel,
+                     keep_signs=args.keep_signs)
         if args.op == "subset":  # bench.py --op subset's contexts
             c.set_window_centre("intlen")
         c.sync()
@@ -52,7 +54,8 @@ def run(args):
         if only is None or v in only:
             order += [(v, 0), (v, 1)]
     manifest = []
-    warm = max(args.warm, rotate) if args.keep_zeros else args.warm  # steady state: every set clean first
+    # steady state: every set clean first, and built by k_keep once more (its sign map established)
+    warm = max(args.warm, 2 * rotate) if args.keep_zeros else args.warm
     for v, t in order:
         for c in ctxs:
             c.set_tuning(variant=v, tile_order=t)
@@ -65,11 +68,12 @@ def run(args):
         manifest.append({"variant": v, "tile_order": t, "dispatches": n, "warm": warm})
     chunk_kb = ctxs[0].tuning().get("pyramid_chunk_kb", 0)
     keep_kernel = ctxs[0].tuning()["keep_kernel"] if args.keep_zeros else 0
+    keep_signs = ctxs[0].tuning()["keep_signs"] if keep_kernel else 0
     for c in ctxs:
         c.close()
     with open(args.manifest, "w") as f:
         json.dump({"config": args.config, "op": args.op, "rotate": rotate, "zero_window": args.zero_window,
-                   "keep_zeros": args.keep_zeros, "keep_kernel": keep_kernel, "band_of": args.band_of, "band": [r0, r1], "instances": manifest,
+                   "keep_zeros": args.keep_zeros, "keep_kernel": keep_kernel, "keep_signs": keep_signs, "band_of": args.band_of, "band": [r0, r1], "instances": manifest,
                    "image_stride_mb": int(os.environ["GDP_IMAGE_STRIDE_MB"]) if os.environ.get("GDP_IMAGE_STRIDE_MB")
                    else None, "pyramid_chunk_kb": chunk_kb}, f)
 
@@ -131,6 +135,7 @@ def summarise(args):
                "op": "build_kept" if man.get("keep_zeros") else man.get("op", "build"),
                "keep_zeros": man.get("keep_zeros", 0),
                "keep_kernel": man.get("keep_kernel", 0),
+               "keep_signs": man.get("keep_signs", 0),
                "zero_window": man.get("zero_window", 0),
                **({"band_of": band_of, "band_rows": [r0, r1]} if band_of else {}),
                **({"image_stride_mb": man["image_stride_mb"]} if man.get("image_stride_mb") else {}),
@@ -145,7 +150,7 @@ def summarise(args):
                "correction": "read = 2 x FETCH_SIZE KiB (gfx950 half-count of wide streaming reads); write = WRITE_SIZE KiB"}
         tag = man["config"] + (f"b{band_of}" if band_of else "") + ("_subset" if man.get("op") == "subset" else "")
         zw = ("z1" if man.get("zero_window", 0) else "") + (f"s{man['image_stride_mb']}" if man.get("image_stride_mb") else "") \
-            + (f"k{man['pyramid_chunk_kb']}" if man.get("pyramid_chunk_kb") else "") + ("kept" if man.get("keep_zeros") else "") + (f"kk{man['keep_kernel']}" if man.get("keep_kernel") else "")
+            + (f"k{man['pyramid_chunk_kb']}" if man.get("pyramid_chunk_kb") else "") + ("kept" if man.get("keep_zeros") else "") + (f"kk{man['keep_kernel']}" if man.get("keep_kernel") else "") + ("ks1" if man.get("keep_signs") else "")
         out = os.path.join(REPO, "profiles", f"pmc_{tag}_v{m['variant']}o{m['tile_order']}{zw}_{args.round}.json")
         if os.path.exists(out) and not args.overwrite:
             print("keep", out)
@@ -173,6 +178,9 @@ def main():
                     help="GDP_TUNE_KEEP_KERNEL of the steady-state builds (with --keep-zeros 1): 0 k_build's keep path, "
                          "1 / 2 k_keep (records ...keptkk<N>_*.json, whose `kernel` names k_keep; the variant then only "
                          "names the first, full build)")
+    ap.add_argument("--keep-signs", type=int, default=None, choices=[0, 1],
+                    help="GDP_TUNE_KEEP_SIGNS of the k_keep builds: 1 (the library's default) skip the level-S+2 stores of "
+                         "rows with no negative pixel (records ...keptkk<N>ks1_*.json), 0 store them all")
     ap.add_argument("--variants", default=None, help="comma-separated variant numbers to profile (default: all)")
     ap.add_argument("--band-of", type=int, default=None,
                     help="row-band config: profile rank 0's band of N ranks (bench.py --gpus N --config c5's "
