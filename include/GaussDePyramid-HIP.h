@@ -96,6 +96,12 @@ public:
     // |interp| > contrast, the edge test when edge_ratio != 0), sorted like gdp_download_refined.
     // Pending host edits of GaussPy are uploaded first; the pyramid itself is not changed.
     std::vector<gdp_keypoint_refined> RefineKeypoints(float contrast = 0.f, float edge_ratio = 0.f);
+    // Extension: orientations of the last RefineKeypoints' records, assigned on the device
+    // (gdp_orient_keypoints in gdp.h has the exact rule: the Gaussian level rebuilt from levels
+    // s..S+2, a 36-bin gradient histogram, one record per peak within 80 % of the highest), sorted
+    // like gdp_download_oriented.  Pending host edits of GaussPy are uploaded first; the pyramid
+    // itself is not changed.  At most twice the keypoint capacity records come back.
+    std::vector<gdp_keypoint_oriented> OrientKeypoints();
     ~GaussPyramid_hip();
     bool initialized;
     bool mirror_host;  // GaussPy two-way: upload before / download after every mutating call (default true)
@@ -141,6 +147,7 @@ protected:
     bool armed_;  // the device pyramid equals host_ as of its last arming and the pages written
                   // since are recorded: the next mutating call may upload only those
     bool defer_;  // DeferDownload: mutating calls end in gdp_host_defer instead of SyncHost
+    gdp_orient* orient_ = nullptr;  // OrientKeypoints' state, created on its first call, destroyed before ctx_
     // rows_in_mirror_() is a walk over every row pointer (41k at 4096^2, tens of microseconds):
     // each public call takes it once (CallScope) and its helpers reuse the answer — the caller
     // cannot re-seat a row while one of its calls runs
@@ -403,6 +410,28 @@ inline std::vector<gdp_keypoint_refined> GaussPyramid_hip::RefineKeypoints(float
     return out;
 }
 
+inline std::vector<gdp_keypoint_oriented> GaussPyramid_hip::OrientKeypoints() {
+    CallScope scope(this);
+    const bool clean = armed_;
+    pull_host_();
+    armed_ = clean;  // the orientation leaves the device pyramid alone, like the detection
+    auto check = [](gdp_orient* w, int status) {
+        if (status != GDP_OK) {
+            std::fprintf(stderr, "GaussPyramid_hip::OrientKeypoints failed: %s (%s)\n", gdp_status_string(status),
+                         gdp_orient_last_error(w));
+            std::abort();
+        }
+    };
+    if (!orient_) check(nullptr, gdp_orient_create(&orient_, ctx_, 0));
+    check(orient_, gdp_orient_keypoints(orient_, nullptr));
+    size_t found = 0, stored = 0;
+    check(orient_, gdp_oriented_count(orient_, 0, &found));
+    std::vector<gdp_keypoint_oriented> out(found);
+    check(orient_, gdp_download_oriented(orient_, 0, out.data(), out.size(), &stored, nullptr));
+    out.resize(stored);
+    return out;
+}
+
 inline void GaussPyramid_hip::output() {  // :89-104
     int len = length;
     for (int i = 0; i < layer; ++i) {
@@ -434,6 +463,7 @@ inline GaussPyramid_hip::~GaussPyramid_hip() {
         delete[] data;
     }
     delete[] filter;
+    gdp_orient_destroy(orient_);
     gdp_destroy(ctx_);
 }
 

@@ -194,8 +194,8 @@ int gdp_device_input(const gdp_ctx* ctx, int b, const void** rows, size_t* pitch
  * a caller needs no host copy of the pyramid to find them.  It runs on whatever the pyramid
  * CURRENTLY holds (the context's own buffer or one bound with gdp_set_output_device): most
  * meaningful after gdp_build_gaussian, whose DoG is a real scale space, but the reference's window
- * pyramid works too.  gdp_refine_keypoints (below) localises them to sub-sample precision.  Out of
- * scope: orientation assignment, descriptors.
+ * pyramid works too.  gdp_refine_keypoints (below) localises them to sub-sample precision and
+ * gdp_orient_keypoints (below it) assigns their orientations.  Out of scope: descriptors.
  *
  * For image b and octave o (rows x cols as held by the context), levels 0..S+1 are taken as the
  * DoG levels D; level S+2 is never read.  Candidates are s in [1, S], r in [1, rows-2],
@@ -319,6 +319,108 @@ int gdp_device_refined(const gdp_ctx* ctx, int b, const gdp_keypoint_refined** r
  * (`value` is not used), n <= the keypoint capacity; anything else is GDP_ERR_ARG and changes
  * nothing. */
 int gdp_upload_keypoints(gdp_ctx* ctx, int b, const gdp_keypoint* host, size_t n);
+
+/* ---- extension: keypoint orientation assignment on the device ---------------------------------
+ * The SIFT step after localisation, done where the pyramid and the refined list already are (no
+ * reference counterpart, no parity claim): a gradient-orientation histogram of the Gaussian level
+ * around every refined record, whose peaks give the keypoint its angle(s).  The Gaussian levels are
+ * not stored, but the pyramid keeps the last one in level S+2 and DoG_t = G_t - G_{t+1}, so G_s is a
+ * suffix sum of levels the context holds; with the order of the additions fixed it is specified bit
+ * for bit.  It reads levels s..S+2 of the CURRENT pyramid (own or bound) and writes nothing of the
+ * context's: its state is an object of its own, gdp_orient, created from a const context.
+ *
+ * The rule.  Every operation is a separately rounded float32 operation: no contraction, denormals
+ * kept, `/` and sqrtf IEEE-correct.  For a refined record (o, s, r, c) with 1 <= s <= S, 1 <= r <=
+ * rows-2, 1 <= c <= cols-2 (a record that names no such sample is dropped before any address is
+ * formed from it), with P[t] the levels of octave o; only the integer sample is used, dscale, drow
+ * and dcol are copied through, not read:
+ *   Gaussian level   L = P[S+2];  for t = S+1 down to s:  L = L + P[t]  (element by element; levels
+ *                    below s are never read)
+ *   window           radius R_s = (9 + s) / (s + 1) in integer division — ceil(3 * 1.5 * sigma_s) with
+ *                    sigma_s = 2 / (s + 1), gdp_conv_taps' schedule: 5, 3, 3, 2, 2, ..., at least 1;
+ *                    weights w_s[d2] = expf(-((float)d2 * k_s)), d2 = 0 .. 2 R_s^2, with
+ *                    k_s = (float)((s+1)*(s+1)) / 18.0f, computed on the HOST with glibc expf and
+ *                    uploaded, as the window taps are (gdp_orient_weights returns them)
+ *   samples          (dr, dc) in [-R, R]^2, rr = r + dr, cc = c + dc; skipped when rr is outside
+ *                    [1, rows-2] or cc outside [1, cols-2]; otherwise
+ *                      gx = L[rr][cc+1] - L[rr][cc-1]      gy = L[rr+1][cc] - L[rr-1][cc]
+ *                      m  = sqrtf(gx*gx + gy*gy)
+ *                    !(m < INFINITY) (NaN or inf) rejects the whole record; !(m > 0.0f) skips the sample
+ *   bin              no atan2.  The quadrant:  q = 0 when gx > 0 && gy >= 0, (ax, ay) = (gx, gy);
+ *                    q = 1 when gx <= 0 && gy > 0, (ax, ay) = (gy, -gx);  q = 2 when gx < 0 && gy <= 0,
+ *                    (ax, ay) = (-gx, -gy);  q = 3 otherwise, (ax, ay) = (-gy, gx).  j = the number of
+ *                    k in 1..8 with ay >= ax * T[k], T[k] the float32 nearest to tan(k * 10 degrees):
+ *                      T[1..8] = 0x3e348f0f 0x3eba5a4e 0x3f13cd3a 0x3f56cf3c
+ *                                0x3f988b62 0x3fddb3d7 0x402fd6ac 0x40b57b24      (bit patterns)
+ *                    bin = 9*q + j.  Angles run from the +col axis towards the +row axis:
+ *                    (gx, gy) = (1,0) -> 0, (0,1) -> 9, (-1,0) -> 18, (0,-1) -> 27, (1,1) -> 4
+ *   histogram        per window row dr a partial part_dr[36] starts at +0 and takes its samples in
+ *                    ascending dc:  part[bin] = part[bin] + m * w_s[dr*dr + dc*dc];  then hist starts
+ *                    at +0 and takes the rows in ascending dr:  hist[k] = hist[k] + part_dr[k]  (a
+ *                    skipped row is a partial of +0; all terms are >= 0, so adding +0 is the identity)
+ *   smoothing        indices mod 36:
+ *                      h[k] = ((hist[k-2] + hist[k+2]) * 0.0625f + (hist[k-1] + hist[k+1]) * 0.25f)
+ *                             + hist[k] * 0.375f
+ *                    the record is rejected unless fabsf(h[k]) < INFINITY for every k
+ *   peaks            mx = h[0]; for k = 1..35: if (h[k] > mx) mx = h[k];  thr = mx * 0.8f;  bin k is a
+ *                    peak when h[k] > h[k-1] && h[k] > h[k+1] && h[k] >= thr; with l = h[k-1], rt = h[k+1]
+ *                      b = (float)k + (0.5f * (l - rt)) / ((l - 2.0f*h[k]) + rt)
+ *                      if (b < 0.0f) b = b + 36.0f;   if (b >= 36.0f) b = b - 36.0f;
+ *                      angle = b * 10.0f                                   (degrees, [0, 360))
+ * One output record per peak (a record without a peak — a flat window — yields none): the result is
+ * an exact multiset. */
+typedef struct gdp_keypoint_oriented {   /* 48 bytes, three 16-B stores */
+    /* bytes 0..31: the input gdp_keypoint_refined, copied */
+    uint16_t octave; uint8_t scale; int8_t kind; int32_t row, col; float value;
+    float dscale, drow, dcol, interp;
+    float angle;      /* degrees, [0, 360) */
+    float peak;       /* h[k] of this peak */
+    uint32_t bin;     /* k */
+    uint32_t peaks;   /* records this input produced (>= 1) */
+} gdp_keypoint_oriented;
+typedef struct gdp_orient gdp_orient;
+/* An orientation object bound to one whole-image context (a row band is GDP_ERR_STATE: the window
+ * crosses band edges).  It owns the weight table, a [batch][capacity_per_image] output buffer with
+ * [batch] uint32 counters and the caller's input lists; capacity_per_image = 0 means twice the
+ * context's keypoint capacity at creation.  The context is only read — its pyramid, geometry and
+ * refined list are looked up at every launch, so gdp_set_keypoint_capacity, gdp_set_output_device
+ * and rebuilds in between are harmless — and must outlive the object: destroy the object first.
+ * gdp_orient_last_error(w) describes w's last failure (w NULL: this thread's last failed create). */
+int gdp_orient_create(gdp_orient** out, const gdp_ctx* ctx, size_t capacity_per_image);
+void gdp_orient_destroy(gdp_orient* w);
+const char* gdp_orient_last_error(const gdp_orient* w);
+/* Make host[0..n) image b's input list instead of the context's refined list (blocking): the way
+ * to orient points of the caller's own.  Every record is validated on the host as
+ * gdp_upload_keypoints does (octave, scale in [1, S], row, col, kind), n <= the object's capacity;
+ * anything else is GDP_ERR_ARG and changes nothing.  host = NULL goes back to the context's list. */
+int gdp_orient_set_input(gdp_orient* w, int b, const gdp_keypoint_refined* host, size_t n);
+/* Orient every image's list: zeroes the counters on `stream` (NULL = the context's own stream),
+ * then ONE launch over all images; asynchronous and stream-ordered.  The input of an image is the
+ * caller's list if one is set, else the first min(refined counter, keypoint capacity) records of the
+ * context's refined list, read on the device — the host never reads that counter, so launching this
+ * right after gdp_refine_keypoints on the same stream is the normal use.  GDP_ERR_STATE when an
+ * image has neither a list of the caller's nor a refined buffer (gdp_device_refined's condition).
+ * More records may be produced than the capacity holds: the counter still counts them all, the
+ * buffer then holds exactly `capacity` true records (which ones is unspecified; a keypoint's
+ * records need not all be among them) and nothing is stored at or beyond it.  The device order is
+ * unspecified. */
+int gdp_orient_keypoints(gdp_orient* w, void* stream);
+/* Records the last orientation produced for image b (blocking; waits for the context's OWN stream;
+ * 0 before any). */
+int gdp_oriented_count(gdp_orient* w, int b, size_t* found);
+/* Copy min(found, the object's capacity, `capacity`) records of image b to `host` (blocking), sorted
+ * ascending by (octave, scale, row, col, bin), ties by the record's twelve 32-bit words compared as
+ * unsigned in memory order, so host results are the same run to run.  *stored = records written,
+ * *found = gdp_oriented_count (either may be NULL). */
+int gdp_download_oriented(gdp_orient* w, int b, gdp_keypoint_oriented* host, size_t capacity,
+                          size_t* stored, size_t* found);
+/* Zero-copy view for device consumers: image b's records (capacity records, the first
+ * min(*count, capacity) valid, device order) and its counter. */
+int gdp_device_oriented(const gdp_orient* w, int b, const gdp_keypoint_oriented** records,
+                        const uint32_t** count);
+/* The window of scale s in a pyramid of S: weights[d2] = w_s[d2] for d2 = 0 .. 2R*R (at most 51
+ * floats) and the radius R.  Pure host computation: no device, no context. */
+int gdp_orient_weights(int S, int scale, float* weights /* 2R*R+1, at most 51 */, int* radius);
 
 /* ---- output --------------------------------------------------------------------------------
  * The blocking copies below are ordered after work on the context's OWN stream; if a build was

@@ -127,6 +127,15 @@ SIGNATURES = {
     "gdp_download_refined": (_c_int, [_p, _c_int, _p, _c_size, ctypes.POINTER(_c_size)]),
     "gdp_device_refined": (_c_int, [_p, _c_int, _pp, _pp]),
     "gdp_upload_keypoints": (_c_int, [_p, _c_int, _p, _c_size]),
+    "gdp_orient_create": (_c_int, [_pp, _p, _c_size]),
+    "gdp_orient_destroy": (None, [_p]),
+    "gdp_orient_last_error": (ctypes.c_char_p, [_p]),
+    "gdp_orient_set_input": (_c_int, [_p, _c_int, _p, _c_size]),
+    "gdp_orient_keypoints": (_c_int, [_p, _p]),
+    "gdp_oriented_count": (_c_int, [_p, _c_int, ctypes.POINTER(_c_size)]),
+    "gdp_download_oriented": (_c_int, [_p, _c_int, _p, _c_size, ctypes.POINTER(_c_size), ctypes.POINTER(_c_size)]),
+    "gdp_device_oriented": (_c_int, [_p, _c_int, _pp, _pp]),
+    "gdp_orient_weights": (_c_int, [_c_int, _c_int, _p, ctypes.POINTER(_c_int)]),
     "gdp_checksum": (_c_int, [_p, _c_int, ctypes.POINTER(ctypes.c_uint64)]),
     "gdp_get_taps": (_c_int, [_p, _c_int, _c_int, _c_int, _p]),
     "gdp_set_window_centre": (_c_int, [_p, _c_int]),
@@ -189,9 +198,11 @@ def build_variants():
     return list(ids)
 
 
-def check(status, ctx=None):
+def check(status, ctx=None, orient=False):
+    """Raise GdpError for a non-zero status; `ctx` is the context whose gdp_last_error describes it
+    (orient=True: a gdp_orient object, or None for a failed gdp_orient_create)."""
     if status != GDP_OK:
         L = lib()
-        msg = L.gdp_last_error(ctx)
+        msg = L.gdp_orient_last_error(ctx) if orient else L.gdp_last_error(ctx)
         raise GdpError(status, (msg or b"").decode() or L.gdp_status_string(status).decode())
     return status

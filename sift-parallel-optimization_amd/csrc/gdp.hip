@@ -55,6 +55,7 @@ namespace {
 #include "gdp_conv.inc"
 #include "gdp_extrema.inc"
 #include "gdp_refine.inc"
+#include "gdp_orient.inc"
 #include "gdp_util.inc"
 #include "gdp_track.inc"
 
@@ -219,6 +220,30 @@ struct gdp_ctx {
     hipStream_t pick(void* s) const {
         if (s == GDP_STREAM_NULL) return (hipStream_t)0;
         return s ? (hipStream_t)s : stream;
+    }
+};
+
+// gdp_orient_create: orientation assignment's state.  It lives outside the context on purpose: the
+// orientation only READS the context (pyramid, geometry, refined list — all looked up at launch
+// time), so no export of it takes a mutable gdp_ctx* and the build that follows stays a kept one.
+struct gdp_orient {
+    const gdp_ctx* ctx = nullptr;
+    size_t capacity = 0;                   // oriented records kept per image; also the longest list of the caller's
+    float* d_weights = nullptr;            // [S][kOrWeights]: w_s[d2] of scale s at (s - 1) * kOrWeights
+    gdp_keypoint_oriented* d_out = nullptr; // [batch][capacity]
+    uint32_t* d_count = nullptr;           // [batch]
+    gdp_keypoint_refined* d_in = nullptr;  // [batch][capacity]: the caller's lists, allocated on first use
+    uint32_t* d_in_count = nullptr;        // [batch]: their lengths; kOrNoList = the context's refined list
+    std::vector<uint32_t> in_count;        // host copy of d_in_count
+    std::string err;
+    int status(int code, const char* fmt, ...) {
+        char buf[512];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(buf, sizeof buf, fmt, ap);
+        va_end(ap);
+        err = buf;
+        return code;
     }
 };
 
@@ -692,8 +717,8 @@ static size_t packed_pyramid_bytes(const gdp_ctx* c) {  // gdp_download_pyramid'
     for (int o = 0; o < c->geom.O; ++o) n += (size_t)c->geom.oct[o].rows * c->geom.oct[o].cols * c->geom.L;
     return n * 4;
 }
-template <class F>
-static int settle_deferred(gdp_ctx* c, const char* what, F&& ranges) {
+template <class C, class F>
+static int settle_deferred(C* c, const char* what, F&& ranges) {
     std::lock_guard<std::mutex> lk(g_track_mu);
     if (!track_any_deferred()) return GDP_OK;
     int rc = GDP_OK;
@@ -2918,6 +2943,214 @@ int gdp_upload_keypoints(gdp_ctx* c, int b, const gdp_keypoint* host, size_t n) 
     GDP_HIP(c, hipStreamSynchronize(c->stream));
     return GDP_OK;
 } GDP_ABI_CATCH(c)
+
+// ---- extension: orientation assignment of the refined list (gdp_orient.inc) ----------------------
+// No export below takes a mutable context: the state is the gdp_orient object's, the context is
+// read (k_orient takes the pyramid and the refined list const), so a build that follows is a kept one.
+static int orient_exception(gdp_orient* w, int code, const char* what) noexcept {
+    try {
+        if (w)
+            w->err = what;
+        else
+            g_create_error = what;
+    } catch (...) {
+    }
+    return code;
+}
+#define GDP_ORIENT_CATCH(w)                                                                                   \
+    catch (const std::bad_alloc&) { return orient_exception((w), GDP_ERR_NOMEM, "host allocation failed (std::bad_alloc)"); } \
+    catch (const std::exception& e_) { return orient_exception((w), GDP_ERR_INTERNAL, e_.what()); }         \
+    catch (...) { return orient_exception((w), GDP_ERR_INTERNAL, "unknown C++ exception"); }
+
+// w_s[d2] = expf(-((float)d2 * k_s)), k_s = (float)((s+1)^2) / 18.0f, for d2 = 0 .. 2 R_s^2; returns R_s
+static int orient_weights_of(int s, float* out) {
+    const int R = or_radius(s);
+    const float k = (float)((s + 1) * (s + 1)) / 18.0f;
+    for (int d2 = 0; d2 <= 2 * R * R; ++d2) out[d2] = expf(-((float)d2 * k));
+    return R;
+}
+
+int gdp_orient_weights(int S, int scale, float* weights, int* radius) try {
+    if (S < 1 || scale < 1 || scale > S || !weights || !radius) return GDP_ERR_ARG;
+    *radius = orient_weights_of(scale, weights);
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+void gdp_orient_destroy(gdp_orient* w) {
+    if (!w) return;
+    (void)hipSetDevice(w->ctx->device);
+    (void)hipDeviceSynchronize();  // a launch on any stream may still read or write the buffers
+    if (w->d_weights) (void)hipFree(w->d_weights);
+    if (w->d_out) (void)hipFree(w->d_out);
+    if (w->d_count) (void)hipFree(w->d_count);
+    if (w->d_in) (void)hipFree(w->d_in);
+    if (w->d_in_count) (void)hipFree(w->d_in_count);
+    delete w;
+}
+
+int gdp_orient_create(gdp_orient** out, const gdp_ctx* c, size_t capacity_per_image) try {
+    if (!out || !c) return GDP_ERR_ARG;
+    auto fail = [&](int code, const std::string& m) {
+        g_create_error = m;
+        return code;
+    };
+    const Geom& g = c->geom;
+    if (g.in_row0 != 0 || g.in_rows != g.H)
+        return fail(GDP_ERR_STATE, "gdp_orient_create: a row band does not hold its keypoints' windows across the band "
+                                   "edges; orient on a whole-image context");
+    const size_t batch = (size_t)g.batch;
+    if (capacity_per_image == 0) {
+        if (c->kp_capacity > SIZE_MAX / 2) return fail(GDP_ERR_ARG, "gdp_orient_create: capacity does not fit the address space");
+        capacity_per_image = 2 * c->kp_capacity;
+    }
+    if (capacity_per_image > (SIZE_MAX / sizeof(gdp_keypoint_oriented)) / batch)
+        return fail(GDP_ERR_ARG, "gdp_orient_create: capacity does not fit the address space");
+    hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    gdp_orient* w = new gdp_orient;
+    w->ctx = c;
+    w->capacity = capacity_per_image;
+    w->in_count.assign(batch, kOrNoList);
+    std::vector<float> table((size_t)std::max(g.S, 1) * kOrWeights, 0.0f);
+    for (int s = 1; s <= g.S; ++s) (void)orient_weights_of(s, table.data() + (size_t)(s - 1) * kOrWeights);
+    e = hipMalloc(reinterpret_cast<void**>(&w->d_weights), table.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(w->d_weights, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_out), w->capacity * batch * sizeof(gdp_keypoint_oriented));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_count), batch * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(w->d_count, 0, batch * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_in_count), batch * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(w->d_in_count, 0xff, batch * sizeof(uint32_t));  // kOrNoList
+    // hipMemset runs on the null stream, which the context's non-blocking stream does not wait for
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        const std::string m = std::string("gdp_orient_create (") + std::to_string(w->capacity) + " records x " +
+                              std::to_string(batch) + " images): " + hipGetErrorString(e);
+        gdp_orient_destroy(w);
+        return fail(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, m);
+    }
+    *out = w;
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+const char* gdp_orient_last_error(const gdp_orient* w) { return w ? w->err.c_str() : g_create_error.c_str(); }
+
+int gdp_orient_set_input(gdp_orient* w, int b, const gdp_keypoint_refined* host, size_t n) try {
+    if (!w) return GDP_ERR_ARG;
+    const gdp_ctx* c = w->ctx;
+    const Geom& g = c->geom;
+    if (b < 0 || b >= g.batch) return w->status(GDP_ERR_ARG, "gdp_orient_set_input: bad argument");
+    if (host && n > w->capacity)
+        return w->status(GDP_ERR_ARG, "gdp_orient_set_input: %zu records exceed the capacity %zu", n, w->capacity);
+    GDP_HIP(w, hipSetDevice(c->device));
+    if (host && n) GDP_SETTLE(w, "gdp_orient_set_input", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint_refined)); });
+    for (size_t i = 0; host && i < n; ++i) {
+        const gdp_keypoint_refined& k = host[i];
+        const bool ok = (int)k.octave < g.O && k.scale >= 1 && (int)k.scale <= g.S && k.row >= 1 &&
+                        k.row <= g.oct[std::min<int>(k.octave, g.O - 1)].rows - 2 && k.col >= 1 &&
+                        k.col <= g.oct[std::min<int>(k.octave, g.O - 1)].cols - 2 && (k.kind == 1 || k.kind == -1);
+        if (!ok)
+            return w->status(GDP_ERR_ARG, "gdp_orient_set_input: record %zu (octave %d, scale %d, row %d, col %d, kind %d) names "
+                                          "no sample of this context", i, (int)k.octave, (int)k.scale, (int)k.row, (int)k.col, (int)k.kind);
+    }
+    if (host && !w->d_in) {
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&w->d_in), w->capacity * (size_t)g.batch * sizeof(gdp_keypoint_refined));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            w->d_in = nullptr;
+            return w->status(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, "gdp_orient_set_input: input buffer: %s", hipGetErrorString(e));
+        }
+    }
+    const uint32_t count = host ? (uint32_t)n : kOrNoList;
+    if (host && n)
+        GDP_HIP(w, hipMemcpyAsync(w->d_in + (size_t)b * w->capacity, track_dma_ptr(host), n * sizeof(gdp_keypoint_refined),
+                                  hipMemcpyHostToDevice, c->stream));
+    GDP_HIP(w, hipMemcpyAsync(w->d_in_count + b, &count, sizeof count, hipMemcpyHostToDevice, c->stream));
+    GDP_HIP(w, hipStreamSynchronize(c->stream));
+    w->in_count[(size_t)b] = count;
+    return GDP_OK;
+} GDP_ORIENT_CATCH(w)
+
+int gdp_orient_keypoints(gdp_orient* w, void* stream) try {
+    if (!w) return GDP_ERR_ARG;
+    const gdp_ctx* c = w->ctx;
+    const Geom& g = c->geom;
+    // inputs of the longest list: the caller's lengths are known here, the context's only on the device
+    unsigned long long longest = 0;
+    for (int b = 0; b < g.batch; ++b) {
+        const uint32_t n = w->in_count[(size_t)b];
+        if (n == kOrNoList && (!c->d_rf || !c->d_rf_count))
+            return w->status(GDP_ERR_STATE, "gdp_orient_keypoints: image %d has no input list and the context no refined "
+                                            "buffer yet (run gdp_refine_keypoints or gdp_orient_set_input first)", b);
+        longest = std::max<unsigned long long>(longest, n == kOrNoList ? c->kp_capacity : n);
+    }
+    // a record yields at most 18 peaks (strict local maxima of 36 circular bins); the counter is 32-bit
+    if (w->capacity > 0xffffffffull || longest * 18 >= (1ull << 32))
+        return w->status(GDP_ERR_ARG, "gdp_orient_keypoints: too many records for the 32-bit counter");
+    const unsigned long long per_img = std::max<unsigned long long>(1, (longest + kOrPerBlock - 1) / kOrPerBlock);
+    if (per_img * (unsigned long long)g.batch >= (1ull << 31))
+        return w->status(GDP_ERR_ARG, "gdp_orient_keypoints: too many records for one launch");
+    GDP_HIP(w, hipSetDevice(c->device));
+    hipStream_t st = c->pick(stream);
+    GDP_HIP(w, hipMemsetAsync(w->d_count, 0, (size_t)g.batch * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_orient, dim3((unsigned)(per_img * g.batch)), dim3(kOrBlock), 0, st, c->d_geom, c->d_out,
+                       reinterpret_cast<const uint4*>(c->d_rf), c->d_rf_count, (unsigned long long)c->kp_capacity,
+                       reinterpret_cast<const uint4*>(w->d_in), w->d_in_count, w->d_weights, reinterpret_cast<uint4*>(w->d_out),
+                       w->d_count, (unsigned long long)w->capacity, (unsigned)per_img);
+    GDP_HIP(w, hipGetLastError());
+    return GDP_OK;
+} GDP_ORIENT_CATCH(w)
+
+int gdp_oriented_count(gdp_orient* w, int b, size_t* found) try {
+    if (!w || !found) return w ? w->status(GDP_ERR_ARG, "gdp_oriented_count: bad argument") : GDP_ERR_ARG;
+    const gdp_ctx* c = w->ctx;
+    if (b < 0 || b >= c->geom.batch) return w->status(GDP_ERR_ARG, "gdp_oriented_count: bad argument");
+    GDP_HIP(w, hipSetDevice(c->device));
+    uint32_t n = 0;
+    GDP_HIP(w, hipMemcpyAsync(&n, w->d_count + b, sizeof n, hipMemcpyDeviceToHost, c->stream));
+    GDP_HIP(w, hipStreamSynchronize(c->stream));
+    *found = n;
+    return GDP_OK;
+} GDP_ORIENT_CATCH(w)
+
+int gdp_download_oriented(gdp_orient* w, int b, gdp_keypoint_oriented* host, size_t capacity, size_t* stored, size_t* found) try {
+    if (!w) return GDP_ERR_ARG;
+    const gdp_ctx* c = w->ctx;
+    if (b < 0 || b >= c->geom.batch || (!host && capacity)) return w->status(GDP_ERR_ARG, "gdp_download_oriented: bad argument");
+    if (stored) *stored = 0;
+    size_t total = 0;
+    const int rc = gdp_oriented_count(w, b, &total);
+    if (rc != GDP_OK) return rc;
+    if (found) *found = total;
+    const size_t n = std::min(total, std::min(w->capacity, capacity));
+    if (n == 0) return GDP_OK;
+    GDP_SETTLE(w, "gdp_download_oriented", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint_oriented)); });
+    GDP_HIP(w, hipMemcpyAsync(track_dma_ptr(host), w->d_out + (size_t)b * w->capacity, n * sizeof(gdp_keypoint_oriented),
+                              hipMemcpyDeviceToHost, c->stream));
+    GDP_HIP(w, hipStreamSynchronize(c->stream));
+    // the device order depends on the waves' timing, and two inputs may name the same sample: the
+    // position and the bin first, then the record's words, so equal keys are identical records
+    std::sort(host, host + n, [](const gdp_keypoint_oriented& p, const gdp_keypoint_oriented& q) {
+        if (p.octave != q.octave) return p.octave < q.octave;
+        if (p.scale != q.scale) return p.scale < q.scale;
+        if (p.row != q.row) return p.row < q.row;
+        if (p.col != q.col) return p.col < q.col;
+        if (p.bin != q.bin) return p.bin < q.bin;
+        uint32_t a[12], z[12];
+        std::memcpy(a, &p, sizeof a);
+        std::memcpy(z, &q, sizeof z);
+        return std::lexicographical_compare(a, a + 12, z, z + 12);
+    });
+    if (stored) *stored = n;
+    return GDP_OK;
+} GDP_ORIENT_CATCH(w)
+
+int gdp_device_oriented(const gdp_orient* w, int b, const gdp_keypoint_oriented** records, const uint32_t** count) try {
+    if (!w || b < 0 || b >= w->ctx->geom.batch) return GDP_ERR_ARG;
+    if (records) *records = w->d_out + (size_t)b * w->capacity;
+    if (count) *count = w->d_count + b;
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
 
 int gdp_set_window_centre(gdp_ctx* c, int mode) try {
     GDP_WRITES_PYRAMID(c);

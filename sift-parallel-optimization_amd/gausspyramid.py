@@ -67,6 +67,14 @@ REFINED_DTYPE = np.dtype({"names": ["octave", "scale", "kind", "row", "col", "va
                           "offsets": [0, 2, 3, 4, 8, 12, 16, 20, 24, 28], "itemsize": 32})
 
 
+# struct gdp_keypoint_oriented (include/gdp.h): 48 bytes, the first 32 the input gdp_keypoint_refined
+ORIENTED_DTYPE = np.dtype({"names": ["octave", "scale", "kind", "row", "col", "value", "dscale", "drow", "dcol", "interp",
+                                     "angle", "peak", "bin", "peaks"],
+                           "formats": [np.uint16, np.uint8, np.int8, np.int32, np.int32, np.float32, np.float32,
+                                       np.float32, np.float32, np.float32, np.float32, np.float32, np.uint32, np.uint32],
+                           "offsets": [0, 2, 3, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44], "itemsize": 48})
+
+
 class Keypoints(np.ndarray):
     """A KEYPOINT_DTYPE array of the stored records with `found`, the number the detection counted
     (larger than len() when the context's capacity was too small)."""
@@ -105,6 +113,15 @@ def conv_taps(S, scale):
     return t[:2 * r.value + 1].copy(), r.value
 
 
+def orient_weights(S, scale):
+    """(w[0:2R*R+1], R): the orientation window of `scale` in a pyramid of S — w[d2] weighs a sample
+    at squared distance d2 (gdp_orient_weights)."""
+    t = np.zeros(51, np.float32)
+    r = _i()
+    check(lib().gdp_orient_weights(int(S), int(scale), _ptr(t), ctypes.byref(r)))
+    return t[:2 * r.value * r.value + 1].copy(), r.value
+
+
 class PyramidContext:
     """`batch` images of H x W int32 (or the row band [row_begin, row_end)) on one GPU.
 
@@ -131,6 +148,8 @@ class PyramidContext:
             self._dims.append((r.value, c.value, f.value))
         self._bound = None  # keeps a caller's device input alive
         self._kp_capacity = 65536  # gdp_set_keypoint_capacity's default
+        self._orient = ctypes.c_void_p()  # the gdp_orient object, created on first use
+        self._orient_capacity = 0         # 0: twice the keypoint capacity at creation
         self.input_format = "i32"
         if input_format != "i32":
             self.set_input_format(input_format)
@@ -498,6 +517,81 @@ class PyramidContext:
         recs = np.ascontiguousarray(records, dtype=KEYPOINT_DTYPE).reshape(-1)
         check(lib().gdp_upload_keypoints(self._ctx, int(b), _ptr(recs) if recs.size else None, recs.size), self._ctx)
 
+    # ------------------------------------------------------------------ orientation (extension)
+    def _orient_handle(self):
+        """The context's gdp_orient object, created on first use (close() destroys it before the
+        context).  It only reads the context: no call below changes the pyramid or the lists."""
+        if not self._orient.value:
+            w = ctypes.c_void_p()
+            check(lib().gdp_orient_create(ctypes.byref(w), self._ctx, int(self._orient_capacity)), None, orient=True)
+            self._orient = w
+            self._orient_records = self._orient_capacity or 2 * self._kp_capacity  # what the object holds per image
+        return self._orient
+
+    def _drop_orient(self):
+        if getattr(self, "_orient", None) and self._orient.value:
+            lib().gdp_orient_destroy(self._orient)
+            self._orient = ctypes.c_void_p()
+
+    def set_orient_capacity(self, n):
+        """Oriented records kept per image, and the longest list set_orient_input takes (default:
+        twice the keypoint capacity when the first orientation call is made).  Drops the earlier
+        results and input lists."""
+        if int(n) <= 0:
+            raise ValueError("the orientation capacity must be > 0")
+        self._drop_orient()
+        self._orient_capacity = int(n)
+
+    def set_orient_input(self, recs, b=0):
+        """Make `recs` (REFINED_DTYPE, or anything numpy converts to it) image b's orientation input
+        instead of the context's refined list (blocking; gdp_orient_set_input validates every
+        record); None goes back to the refined list."""
+        w = self._orient_handle()
+        if recs is None:
+            check(lib().gdp_orient_set_input(w, int(b), None, 0), w, orient=True)
+            return
+        recs = np.ascontiguousarray(recs, dtype=REFINED_DTYPE).reshape(-1)
+        keep = recs if recs.size else np.zeros(1, REFINED_DTYPE)  # an empty list is still a list: a non-null pointer
+        check(lib().gdp_orient_set_input(w, int(b), _ptr(keep), recs.size), w, orient=True)
+
+    def orient_keypoints(self, stream=None):
+        """Assign orientations to every image's refined list (the last refine_keypoints', or
+        set_orient_input's) on the CURRENT pyramid (gdp_orient_keypoints: the Gaussian level rebuilt
+        from levels s..S+2, a 36-bin gradient histogram, one record per peak); asynchronous on
+        `stream`, one launch, no host read of the counter."""
+        w = self._orient_handle()
+        check(lib().gdp_orient_keypoints(w, _stream_handle(stream)), w, orient=True)
+
+    def oriented_count(self, b=0):
+        """Records the last orientation produced for image b (blocking; may exceed the capacity)."""
+        if not self._orient.value:
+            return 0
+        n = ctypes.c_size_t()
+        check(lib().gdp_oriented_count(self._orient, int(b), ctypes.byref(n)), self._orient, orient=True)
+        return n.value
+
+    def oriented_keypoints(self, b=0):
+        """The stored records of image b as an ORIENTED_DTYPE array sorted by (octave, scale, row,
+        col, bin) and then by the records' words (blocking); its `found` attribute is
+        oriented_count(b)."""
+        if not self._orient.value:
+            return np.zeros(0, ORIENTED_DTYPE).view(Keypoints)
+        w = self._orient
+        out = np.zeros(min(self.oriented_count(b), self._orient_records), ORIENTED_DTYPE)
+        stored, found = ctypes.c_size_t(), ctypes.c_size_t()
+        check(lib().gdp_download_oriented(w, int(b), _ptr(out) if out.size else None, out.size, ctypes.byref(stored),
+                                          ctypes.byref(found)), w, orient=True)
+        out = out[:stored.value].view(Keypoints)
+        out.found = found.value
+        return out
+
+    def device_oriented(self, b=0):
+        """(device address of image b's oriented records, device address of its uint32 counter)."""
+        w = self._orient_handle()
+        recs, count = ctypes.c_void_p(), ctypes.c_void_p()
+        check(lib().gdp_device_oriented(w, int(b), ctypes.byref(recs), ctypes.byref(count)), w, orient=True)
+        return recs.value, count.value
+
     def device_level_ptr(self, b, o, s):
         """Device address of level (o, s) of image b.  Read-only: after writing through it, call
         pyramid_written() before the next build."""
@@ -517,6 +611,7 @@ class PyramidContext:
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
+        self._drop_orient()  # the orientation object goes before its context
         if getattr(self, "_ctx", None) and self._ctx.value:
             lib().gdp_destroy(self._ctx)
             self._ctx = ctypes.c_void_p()
@@ -642,6 +737,14 @@ class GaussPyramid:
         self.SyncDevice()
         self._ctx.refine_keypoints(contrast, edge_ratio)
         return self._ctx.refined_keypoints(0)
+
+    def OrientKeypoints(self):
+        """Extension: assign orientations to the last RefineKeypoints' records on the device
+        (PyramidContext.orient_keypoints) and return one ORIENTED_DTYPE record per histogram peak.
+        Host edits to GaussPy are oriented on; the pyramid is not changed."""
+        self.SyncDevice()
+        self._ctx.orient_keypoints()
+        return self._ctx.oriented_keypoints(0)
 
     def output(self, file=None):
         """:89-104 — print scale 0 of each octave (space separated) and an `==` separator row."""
