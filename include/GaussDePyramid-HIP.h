@@ -102,6 +102,12 @@ public:
     // like gdp_download_oriented.  Pending host edits of GaussPy are uploaded first; the pyramid
     // itself is not changed.  At most twice the keypoint capacity records come back.
     std::vector<gdp_keypoint_oriented> OrientKeypoints();
+    // Extension: the 128-byte SIFT descriptors of the last OrientKeypoints' records, computed on the
+    // device (gdp_describe_keypoints in gdp.h has the exact rule: the Gaussian level rebuilt from
+    // levels s..S+2, a 4 x 4 x 8 gradient histogram rotated to the keypoint's angle, normalised,
+    // clipped and quantised), sorted like gdp_download_described: one record per oriented record.
+    // Pending host edits of GaussPy are uploaded first; the pyramid itself is not changed.
+    std::vector<gdp_keypoint_described> DescribeKeypoints();
     ~GaussPyramid_hip();
     bool initialized;
     bool mirror_host;  // GaussPy two-way: upload before / download after every mutating call (default true)
@@ -148,6 +154,7 @@ protected:
                   // since are recorded: the next mutating call may upload only those
     bool defer_;  // DeferDownload: mutating calls end in gdp_host_defer instead of SyncHost
     gdp_orient* orient_ = nullptr;  // OrientKeypoints' state, created on its first call, destroyed before ctx_
+    gdp_describe* describe_ = nullptr;  // DescribeKeypoints' state, created on its first call, destroyed before orient_
     // rows_in_mirror_() is a walk over every row pointer (41k at 4096^2, tens of microseconds):
     // each public call takes it once (CallScope) and its helpers reuse the answer — the caller
     // cannot re-seat a row while one of its calls runs
@@ -432,6 +439,28 @@ inline std::vector<gdp_keypoint_oriented> GaussPyramid_hip::OrientKeypoints() {
     return out;
 }
 
+inline std::vector<gdp_keypoint_described> GaussPyramid_hip::DescribeKeypoints() {
+    CallScope scope(this);
+    const bool clean = armed_;
+    pull_host_();
+    armed_ = clean;  // the description leaves the device pyramid alone, like the detection
+    auto check = [](const char* last, int status) {
+        if (status != GDP_OK) {
+            std::fprintf(stderr, "GaussPyramid_hip::DescribeKeypoints failed: %s (%s)\n", gdp_status_string(status), last);
+            std::abort();
+        }
+    };
+    if (!orient_) check(gdp_orient_last_error(nullptr), gdp_orient_create(&orient_, ctx_, 0));
+    if (!describe_) check(gdp_describe_last_error(nullptr), gdp_describe_create(&describe_, ctx_, orient_, 0));
+    check(gdp_describe_last_error(describe_), gdp_describe_keypoints(describe_, nullptr));
+    size_t found = 0, stored = 0;
+    check(gdp_describe_last_error(describe_), gdp_described_count(describe_, 0, &found));
+    std::vector<gdp_keypoint_described> out(found);
+    check(gdp_describe_last_error(describe_), gdp_download_described(describe_, 0, out.data(), out.size(), &stored, nullptr));
+    out.resize(stored);
+    return out;
+}
+
 inline void GaussPyramid_hip::output() {  // :89-104
     int len = length;
     for (int i = 0; i < layer; ++i) {
@@ -463,6 +492,7 @@ inline GaussPyramid_hip::~GaussPyramid_hip() {
         delete[] data;
     }
     delete[] filter;
+    gdp_describe_destroy(describe_);
     gdp_orient_destroy(orient_);
     gdp_destroy(ctx_);
 }

@@ -196,6 +196,7 @@ int gdp_device_input(const gdp_ctx* ctx, int b, const void** rows, size_t* pitch
  * meaningful after gdp_build_gaussian, whose DoG is a real scale space, but the reference's window
  * pyramid works too.  gdp_refine_keypoints (below) localises them to sub-sample precision and
  * gdp_orient_keypoints (below it) assigns their orientations.  Out of scope: descriptors.
+ * (That was the scope of this step alone: gdp_describe_keypoints, further below, now provides them.)
  *
  * For image b and octave o (rows x cols as held by the context), levels 0..S+1 are taken as the
  * DoG levels D; level S+2 is never read.  Candidates are s in [1, S], r in [1, rows-2],
@@ -421,6 +422,126 @@ int gdp_device_oriented(const gdp_orient* w, int b, const gdp_keypoint_oriented*
 /* The window of scale s in a pyramid of S: weights[d2] = w_s[d2] for d2 = 0 .. 2R*R (at most 51
  * floats) and the radius R.  Pure host computation: no device, no context. */
 int gdp_orient_weights(int S, int scale, float* weights /* 2R*R+1, at most 51 */, int* radius);
+
+/* ---- extension: SIFT descriptors on the device ------------------------------------------------
+ * The last step of the keypoint chain, done where the pyramid and the oriented list already are (no
+ * reference counterpart, no parity claim): Lowe's 4 x 4 x 8 gradient histogram around every oriented
+ * record, rotated to the keypoint's angle, normalised, clipped and quantised to 128 bytes — something
+ * a caller can match without ever downloading the pyramid.  It reads levels s..S+2 of the CURRENT
+ * pyramid (own or bound) and writes nothing of the context's or the orientation object's: its state
+ * is an object of its own, gdp_describe, created from a const context and a const gdp_orient.
+ *
+ * The rule.  Every operation is a separately rounded float32 operation: no contraction, denormals
+ * kept, `/` and sqrtf IEEE-correct; integer arithmetic is exact.  The result is an exact multiset of
+ * 176-byte records.
+ *   input            a gdp_keypoint_oriented record (o, s, r, c, angle).  It is dropped before any
+ *                    address is formed from it unless 1 <= s <= S, 1 <= r <= rows-2, 1 <= c <= cols-2
+ *                    and 0.0f <= angle && angle < 360.0f (a NaN angle drops it).  Only the integer
+ *                    sample and `angle` are read; everything else is copied through
+ *   Gaussian level   gdp_orient_keypoints' rule:  L = P[S+2];  for t = S+1 down to s:  L = L + P[t]
+ *                    (levels below s are never read)
+ *   window           radius R_s = (2121 + 50*(s+1)) / (100*(s+1)) in integer division — round(3 sigma_s
+ *                    * sqrt(2) * 2.5) with sigma_s = 2 / (s + 1): 11, 7, 5, 4, 4, 3, 3, 2, 2 for
+ *                    s = 1..9;  inv_s = (float)(s+1) / 6.0f, one over the bin width 3 sigma_s
+ *   weights          W_s[d2] = expf(-((float)d2 * k_s)), d2 = 0 .. 2 R_s^2 (at most 243 entries), with
+ *                    k_s = (float)((s+1)*(s+1)) / 288.0f: Lowe's Gaussian of sigma = 2 bins, a function
+ *                    of the integer distance because a rotation keeps distances.  Computed on the HOST
+ *                    with glibc expf and uploaded (gdp_describe_tables returns them); no exp on the device
+ *   rotation         no sin or cos on the device: a table of 1,440 quarter-degree steps built on the
+ *                    host.  Q[m] = (float)cos(m * pi / 720) evaluated in double, m = 0..360, with
+ *                    Q[0] = 1 and Q[360] = 0 set exactly; for a = 360k + m, (C[a], S[a]) is
+ *                    (Q[m], Q[360-m]) rotated k times by (c, s) -> (-s, c).
+ *                      a = (int)(angle * 4.0f + 0.5f);  if (a >= 1440) a -= 1440;
+ *                      ca = C[a],  sa = S[a]
+ *   samples          (dr, dc) in [-R, R]^2, rr = r + dr, cc = c + dc; skipped when rr is outside
+ *                    [1, rows-2] or cc outside [1, cols-2]; otherwise, with x = (float)dc, y = (float)dr
+ *                      cb = ((x*ca + y*sa) * inv_s) + 1.5f
+ *                      rb = ((y*ca - x*sa) * inv_s) + 1.5f
+ *                    skipped unless rb > -1 && rb < 4 && cb > -1 && cb < 4; then
+ *                      gx = L[rr][cc+1] - L[rr][cc-1]      gy = L[rr+1][cc] - L[rr-1][cc]
+ *                      m  = sqrtf(gx*gx + gy*gy)
+ *                    !(m < INFINITY) (NaN or inf) rejects the whole record; !(m > 0.0f) skips the sample
+ *   orientation      no atan2.   gu = gx*ca + gy*sa     gv = gy*ca - gx*sa
+ *                    the quadrant as in gdp_orient_keypoints' rule, applied to (gu, gv):  q = 0 when
+ *                    gu > 0 && gv >= 0, (ax, ay) = (gu, gv);  q = 1 when gu <= 0 && gv > 0, (ax, ay) =
+ *                    (gv, -gu);  q = 2 when gu < 0 && gv <= 0, (ax, ay) = (-gu, -gv);  q = 3 otherwise,
+ *                    (ax, ay) = (-gv, gu).  Then
+ *                      if (ay <= ax)  w8 = (ax > 0) ? A(ay / ax) : 0;   else  w8 = 2.0f - A(ax / ay);
+ *                      ob = (float)(2*q) + w8;   if (ob >= 8.0f) ob = ob - 8.0f;
+ *                    A(t) ~ atan(t) * 4 / pi on [0, 1] is an odd polynomial in Horner form: z = t*t;
+ *                    p = c5;  p = p*z + c4;  ...  p = p*z + c0;  A = p*t  (each * and + rounded), with
+ *                      c0..c5 = 0x3fa2f890 0xbed8d61d 0x3e7c5661 0xbe17cbe9 0x3d89486e 0xbc74784e
+ *                    (bit patterns).  Over the float32 t of [0, 1] its error is at most 2.24e-6 bins
+ *                    (1.0e-4 degrees), it is monotone, and A(1) = 0.99999785 < 1
+ *   trilinear split  r0 = floorf(rb), c0 = floorf(cb), o0 = floorf(ob);  fr = rb - r0, fc = cb - c0,
+ *                    fo = ob - o0;  mag = m * W_s[dr*dr + dc*dc].  As OpenCV splits:  v1 = mag*fr,
+ *                    v0 = mag - v1;  each of those by fc the same way (vc1 = v*fc, vc0 = v - vc1);  each
+ *                    of those by fo the same way.  The eight values go to bins
+ *                    ((r0+i)*4 + (c0+j))*8 + ((o0+k) mod 8), i, j, k in {0, 1}; a value is dropped when
+ *                    r0+i or c0+j is outside [0, 3].  All eight are >= +0 and their targets distinct
+ *   histogram        gdp_orient_keypoints' order: per window row dr a partial part_dr[128] starts at +0
+ *                    and takes its samples in ascending dc; hist starts at +0 and adds the partials in
+ *                    ascending dr (a skipped row is a partial of +0: the identity, every term is >= 0).
+ *                    The record is rejected unless hist[i] < INFINITY for every i
+ *   normalisation    T(v), the tree sum of squares:  t[i] = v[i]*v[i];  for step = 64, 32, ..., 1:
+ *                    t[i] = t[i] + t[i+step] for i < step;  T = t[0].
+ *                      n  = sqrtf(T(hist));   rejected unless n > 0 && n < INFINITY
+ *                      h[i] = hist[i] / n;    if (h[i] > 0.2f) h[i] = 0.2f
+ *                      n2 = sqrtf(T(h))
+ *                      qv = (h[i] / n2) * 512.0f
+ *                      desc[i] = qv >= 255.0f ? 255 : (uint8_t)(int)qv
+ * One output record per input that is neither dropped nor rejected. */
+typedef struct gdp_keypoint_described {  /* 176 bytes, eleven 16-B stores */
+    /* bytes 0..47: the input gdp_keypoint_oriented, copied */
+    uint16_t octave; uint8_t scale; int8_t kind; int32_t row, col; float value;
+    float dscale, drow, dcol, interp;
+    float angle, peak; uint32_t bin, peaks;
+    uint8_t desc[128];   /* [row bin][col bin][orientation bin] */
+} gdp_keypoint_described;
+typedef struct gdp_describe gdp_describe;
+/* A descriptor object bound to one whole-image context (a row band is GDP_ERR_STATE: the window
+ * crosses band edges) and, optionally, to the orientation object `src` of that context whose list it
+ * describes (src = NULL: every image needs a list of the caller's, gdp_describe_set_input).  It owns
+ * the weight and rotation tables, a [batch][capacity_per_image] output buffer with [batch] uint32
+ * counters and the caller's input lists; capacity_per_image = 0 means src's capacity, or the
+ * context's keypoint capacity at creation when src is NULL.  The context and src are only read —
+ * looked up at every launch — and must outlive the object: destroy the object first.
+ * gdp_describe_last_error(w) describes w's last failure (w NULL: this thread's last failed create). */
+int gdp_describe_create(gdp_describe** out, const gdp_ctx* ctx, const gdp_orient* src, size_t capacity_per_image);
+void gdp_describe_destroy(gdp_describe* w);
+const char* gdp_describe_last_error(const gdp_describe* w);
+/* Make host[0..n) image b's input list instead of src's oriented list (blocking): the way to describe
+ * points of the caller's own.  Every record is validated on the host exactly as the device checks it
+ * (octave, scale in [1, S], row, col, and 0 <= angle < 360, a NaN refused), n <= the object's
+ * capacity; anything else is GDP_ERR_ARG and changes nothing.  host = NULL goes back to src's list. */
+int gdp_describe_set_input(gdp_describe* w, int b, const gdp_keypoint_oriented* host, size_t n);
+/* Describe every image's list: zeroes the counters on `stream` (NULL = the context's own stream),
+ * then ONE launch over all images; asynchronous and stream-ordered.  The input of an image is the
+ * caller's list if one is set, else the first min(oriented counter, src's capacity) records of src's
+ * list, read on the device — the host never reads that counter, so launching this right after
+ * gdp_orient_keypoints on the same stream is the normal use.  GDP_ERR_STATE when an image has neither
+ * a list of the caller's nor a src.  Outputs never exceed inputs; with a smaller capacity the counter
+ * still counts every record, the buffer then holds exactly `capacity` true records (which ones is
+ * unspecified) and nothing is stored at or beyond it.  The device order is unspecified. */
+int gdp_describe_keypoints(gdp_describe* w, void* stream);
+/* Records the last description produced for image b (blocking; waits for the context's OWN stream;
+ * 0 before any). */
+int gdp_described_count(gdp_describe* w, int b, size_t* found);
+/* Copy min(found, the object's capacity, `capacity`) records of image b to `host` (blocking), sorted
+ * ascending by (octave, scale, row, col, bin), ties by the record's 44 32-bit words compared as
+ * unsigned in memory order, so host results are the same run to run.  *stored = records written,
+ * *found = gdp_described_count (either may be NULL). */
+int gdp_download_described(gdp_describe* w, int b, gdp_keypoint_described* host, size_t capacity,
+                           size_t* stored, size_t* found);
+/* Zero-copy view for device consumers: image b's records (capacity records, the first
+ * min(*count, capacity) valid, device order) and its counter. */
+int gdp_device_described(const gdp_describe* w, int b, const gdp_keypoint_described** records,
+                         const uint32_t** count);
+/* The tables of scale s in a pyramid of S: weights[d2] = W_s[d2] for d2 = 0 .. 2R*R (at most 243
+ * floats), the radius R, and the rotation table C[0..1440), S[0..1440) (the same for every scale).
+ * Any output pointer but `radius` may be NULL.  Pure host computation: no device, no context. */
+int gdp_describe_tables(int S, int scale, float* weights /* 2R*R+1, at most 243 */, int* radius,
+                        float* cos1440, float* sin1440);
 
 /* ---- output --------------------------------------------------------------------------------
  * The blocking copies below are ordered after work on the context's OWN stream; if a build was

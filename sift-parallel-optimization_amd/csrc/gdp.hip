@@ -56,6 +56,7 @@ namespace {
 #include "gdp_extrema.inc"
 #include "gdp_refine.inc"
 #include "gdp_orient.inc"
+#include "gdp_describe.inc"
 #include "gdp_util.inc"
 #include "gdp_track.inc"
 
@@ -235,6 +236,32 @@ struct gdp_orient {
     gdp_keypoint_refined* d_in = nullptr;  // [batch][capacity]: the caller's lists, allocated on first use
     uint32_t* d_in_count = nullptr;        // [batch]: their lengths; kOrNoList = the context's refined list
     std::vector<uint32_t> in_count;        // host copy of d_in_count
+    std::string err;
+    int status(int code, const char* fmt, ...) {
+        char buf[512];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(buf, sizeof buf, fmt, ap);
+        va_end(ap);
+        err = buf;
+        return code;
+    }
+};
+
+// gdp_describe_create: the descriptors' state.  Like gdp_orient it lives outside the context, and
+// outside the orientation object too: k_describe only READS the pyramid, the geometry and the
+// oriented list (all looked up at launch time), so no export of it takes a mutable gdp_ctx*.
+struct gdp_describe {
+    const gdp_ctx* ctx = nullptr;
+    const gdp_orient* src = nullptr;         // whose oriented list is described; NULL: the caller's lists only
+    size_t capacity = 0;                     // described records kept per image; also the longest list of the caller's
+    float* d_weights = nullptr;              // [S][kDeWeights]: W_s[d2] of scale s at (s - 1) * kDeWeights
+    float* d_rot = nullptr;                  // [2][kDeAngles]: C[a], then S[a]
+    gdp_keypoint_described* d_out = nullptr; // [batch][capacity]
+    uint32_t* d_count = nullptr;             // [batch]
+    gdp_keypoint_oriented* d_in = nullptr;   // [batch][capacity]: the caller's lists, allocated on first use
+    uint32_t* d_in_count = nullptr;          // [batch]: their lengths; kDeNoList = src's list
+    std::vector<uint32_t> in_count;          // host copy of d_in_count
     std::string err;
     int status(int code, const char* fmt, ...) {
         char buf[512];
@@ -3146,6 +3173,244 @@ int gdp_download_oriented(gdp_orient* w, int b, gdp_keypoint_oriented* host, siz
 } GDP_ORIENT_CATCH(w)
 
 int gdp_device_oriented(const gdp_orient* w, int b, const gdp_keypoint_oriented** records, const uint32_t** count) try {
+    if (!w || b < 0 || b >= w->ctx->geom.batch) return GDP_ERR_ARG;
+    if (records) *records = w->d_out + (size_t)b * w->capacity;
+    if (count) *count = w->d_count + b;
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+// ---- extension: SIFT descriptors of the oriented list (gdp_describe.inc) --------------------------
+// No export below takes a mutable context or a mutable orientation object: the state is the
+// gdp_describe object's, everything else is read (k_describe takes the pyramid and the lists const).
+static int describe_exception(gdp_describe* w, int code, const char* what) noexcept {
+    try {
+        if (w)
+            w->err = what;
+        else
+            g_create_error = what;
+    } catch (...) {
+    }
+    return code;
+}
+#define GDP_DESCRIBE_CATCH(w)                                                                                 \
+    catch (const std::bad_alloc&) { return describe_exception((w), GDP_ERR_NOMEM, "host allocation failed (std::bad_alloc)"); } \
+    catch (const std::exception& e_) { return describe_exception((w), GDP_ERR_INTERNAL, e_.what()); }       \
+    catch (...) { return describe_exception((w), GDP_ERR_INTERNAL, "unknown C++ exception"); }
+
+// W_s[d2] = expf(-((float)d2 * k_s)), k_s = (float)((s+1)^2) / 288.0f, for d2 = 0 .. 2 R_s^2; returns R_s
+static int describe_weights_of(int s, float* out) {
+    const int R = de_radius(s);
+    const float k = (float)((s + 1) * (s + 1)) / 288.0f;
+    for (int d2 = 0; out && d2 <= 2 * R * R; ++d2) out[d2] = expf(-((float)d2 * k));
+    return R;
+}
+
+// C[a], S[a], a = 0..1439: Q[m] = (float)cos(m pi / 720) over the first quadrant, Q[0] = 1 and
+// Q[360] = 0 exactly, turned through the other three by (c, s) -> (-s, c); either output may be NULL
+static void describe_rotation(float* cosv, float* sinv) {
+    float Q[kDeAngles / 4 + 1];
+    for (int m = 0; m <= kDeAngles / 4; ++m) Q[m] = (float)cos((double)m * M_PI / 720.0);
+    Q[0] = 1.0f;
+    Q[kDeAngles / 4] = 0.0f;
+    for (int a = 0; a < kDeAngles; ++a) {
+        const int k = a / (kDeAngles / 4), m = a % (kDeAngles / 4);
+        float c = Q[m], s = Q[kDeAngles / 4 - m];
+        for (int t = 0; t < k; ++t) {
+            const float c0 = c;
+            c = -s;
+            s = c0;
+        }
+        if (cosv) cosv[a] = c;
+        if (sinv) sinv[a] = s;
+    }
+}
+
+int gdp_describe_tables(int S, int scale, float* weights, int* radius, float* cos1440, float* sin1440) try {
+    if (S < 1 || S > 60 || scale < 1 || scale > S || !radius) return GDP_ERR_ARG;
+    *radius = describe_weights_of(scale, weights);
+    describe_rotation(cos1440, sin1440);
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+void gdp_describe_destroy(gdp_describe* w) {
+    if (!w) return;
+    (void)hipSetDevice(w->ctx->device);
+    (void)hipDeviceSynchronize();  // a launch on any stream may still read or write the buffers
+    if (w->d_weights) (void)hipFree(w->d_weights);
+    if (w->d_rot) (void)hipFree(w->d_rot);
+    if (w->d_out) (void)hipFree(w->d_out);
+    if (w->d_count) (void)hipFree(w->d_count);
+    if (w->d_in) (void)hipFree(w->d_in);
+    if (w->d_in_count) (void)hipFree(w->d_in_count);
+    delete w;
+}
+
+int gdp_describe_create(gdp_describe** out, const gdp_ctx* c, const gdp_orient* src, size_t capacity_per_image) try {
+    if (!out || !c) return GDP_ERR_ARG;
+    auto fail = [&](int code, const std::string& m) {
+        g_create_error = m;
+        return code;
+    };
+    if (src && src->ctx != c) return fail(GDP_ERR_ARG, "gdp_describe_create: the orientation object belongs to another context");
+    const Geom& g = c->geom;
+    if (g.in_row0 != 0 || g.in_rows != g.H)
+        return fail(GDP_ERR_STATE, "gdp_describe_create: a row band does not hold its keypoints' windows across the band "
+                                   "edges; describe on a whole-image context");
+    const size_t batch = (size_t)g.batch;
+    if (capacity_per_image == 0) capacity_per_image = src ? src->capacity : c->kp_capacity;
+    if (capacity_per_image == 0 || capacity_per_image > (SIZE_MAX / sizeof(gdp_keypoint_described)) / batch)
+        return fail(GDP_ERR_ARG, "gdp_describe_create: capacity does not fit the address space");
+    hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    gdp_describe* w = new gdp_describe;
+    w->ctx = c;
+    w->src = src;
+    w->capacity = capacity_per_image;
+    w->in_count.assign(batch, kDeNoList);
+    std::vector<float> table((size_t)std::max(g.S, 1) * kDeWeights, 0.0f);
+    for (int s = 1; s <= g.S; ++s) (void)describe_weights_of(s, table.data() + (size_t)(s - 1) * kDeWeights);
+    std::vector<float> rot(2 * (size_t)kDeAngles);
+    describe_rotation(rot.data(), rot.data() + kDeAngles);
+    e = hipMalloc(reinterpret_cast<void**>(&w->d_weights), table.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(w->d_weights, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_rot), rot.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(w->d_rot, rot.data(), rot.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_out), w->capacity * batch * sizeof(gdp_keypoint_described));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_count), batch * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(w->d_count, 0, batch * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_in_count), batch * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(w->d_in_count, 0xff, batch * sizeof(uint32_t));  // kDeNoList
+    // hipMemset runs on the null stream, which the context's non-blocking stream does not wait for
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        const std::string m = std::string("gdp_describe_create (") + std::to_string(w->capacity) + " records x " +
+                              std::to_string(batch) + " images): " + hipGetErrorString(e);
+        gdp_describe_destroy(w);
+        return fail(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, m);
+    }
+    *out = w;
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+const char* gdp_describe_last_error(const gdp_describe* w) { return w ? w->err.c_str() : g_create_error.c_str(); }
+
+int gdp_describe_set_input(gdp_describe* w, int b, const gdp_keypoint_oriented* host, size_t n) try {
+    if (!w) return GDP_ERR_ARG;
+    const gdp_ctx* c = w->ctx;
+    const Geom& g = c->geom;
+    if (b < 0 || b >= g.batch) return w->status(GDP_ERR_ARG, "gdp_describe_set_input: bad argument");
+    if (host && n > w->capacity)
+        return w->status(GDP_ERR_ARG, "gdp_describe_set_input: %zu records exceed the capacity %zu", n, w->capacity);
+    GDP_HIP(w, hipSetDevice(c->device));
+    if (host && n) GDP_SETTLE(w, "gdp_describe_set_input", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint_oriented)); });
+    for (size_t i = 0; host && i < n; ++i) {
+        // exactly what k_describe checks before it forms an address
+        const gdp_keypoint_oriented& k = host[i];
+        const bool ok = (int)k.octave < g.O && k.scale >= 1 && (int)k.scale <= g.S && k.row >= 1 &&
+                        k.row <= g.oct[std::min<int>(k.octave, g.O - 1)].rows - 2 && k.col >= 1 &&
+                        k.col <= g.oct[std::min<int>(k.octave, g.O - 1)].cols - 2 && 0.0f <= k.angle && k.angle < 360.0f;
+        if (!ok)
+            return w->status(GDP_ERR_ARG, "gdp_describe_set_input: record %zu (octave %d, scale %d, row %d, col %d, angle %g) names "
+                                          "no sample of this context or no angle in [0, 360)", i, (int)k.octave, (int)k.scale,
+                             (int)k.row, (int)k.col, (double)k.angle);
+    }
+    if (host && !w->d_in) {
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&w->d_in), w->capacity * (size_t)g.batch * sizeof(gdp_keypoint_oriented));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            w->d_in = nullptr;
+            return w->status(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, "gdp_describe_set_input: input buffer: %s", hipGetErrorString(e));
+        }
+    }
+    const uint32_t count = host ? (uint32_t)n : kDeNoList;
+    if (host && n)
+        GDP_HIP(w, hipMemcpyAsync(w->d_in + (size_t)b * w->capacity, track_dma_ptr(host), n * sizeof(gdp_keypoint_oriented),
+                                  hipMemcpyHostToDevice, c->stream));
+    GDP_HIP(w, hipMemcpyAsync(w->d_in_count + b, &count, sizeof count, hipMemcpyHostToDevice, c->stream));
+    GDP_HIP(w, hipStreamSynchronize(c->stream));
+    w->in_count[(size_t)b] = count;
+    return GDP_OK;
+} GDP_DESCRIBE_CATCH(w)
+
+int gdp_describe_keypoints(gdp_describe* w, void* stream) try {
+    if (!w) return GDP_ERR_ARG;
+    const gdp_ctx* c = w->ctx;
+    const gdp_orient* src = w->src;
+    const Geom& g = c->geom;
+    // inputs of the longest list: the caller's lengths are known here, the orientation's only on the device
+    unsigned long long longest = 0;
+    for (int b = 0; b < g.batch; ++b) {
+        const uint32_t n = w->in_count[(size_t)b];
+        if (n == kDeNoList && !src)
+            return w->status(GDP_ERR_STATE, "gdp_describe_keypoints: image %d has no input list and the object no orientation "
+                                            "object to read (gdp_describe_set_input, or create it with one)", b);
+        longest = std::max<unsigned long long>(longest, n == kDeNoList ? src->capacity : n);
+    }
+    // one record per input at most; the counter is 32-bit
+    if (w->capacity > 0xffffffffull || longest >= (1ull << 32))
+        return w->status(GDP_ERR_ARG, "gdp_describe_keypoints: too many records for the 32-bit counter");
+    const unsigned long long per_img = std::max<unsigned long long>(1, (longest + kDePerBlock - 1) / kDePerBlock);
+    if (per_img * (unsigned long long)g.batch >= (1ull << 31))
+        return w->status(GDP_ERR_ARG, "gdp_describe_keypoints: too many records for one launch");
+    GDP_HIP(w, hipSetDevice(c->device));
+    hipStream_t st = c->pick(stream);
+    GDP_HIP(w, hipMemsetAsync(w->d_count, 0, (size_t)g.batch * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_describe, dim3((unsigned)(per_img * g.batch)), dim3(kDeBlock), 0, st, c->d_geom, c->d_out,
+                       reinterpret_cast<const uint4*>(src ? src->d_out : nullptr), src ? src->d_count : nullptr,
+                       (unsigned long long)(src ? src->capacity : 0), reinterpret_cast<const uint4*>(w->d_in), w->d_in_count,
+                       w->d_weights, w->d_rot, reinterpret_cast<uint4*>(w->d_out), w->d_count,
+                       (unsigned long long)w->capacity, (unsigned)per_img);
+    GDP_HIP(w, hipGetLastError());
+    return GDP_OK;
+} GDP_DESCRIBE_CATCH(w)
+
+int gdp_described_count(gdp_describe* w, int b, size_t* found) try {
+    if (!w || !found) return w ? w->status(GDP_ERR_ARG, "gdp_described_count: bad argument") : GDP_ERR_ARG;
+    const gdp_ctx* c = w->ctx;
+    if (b < 0 || b >= c->geom.batch) return w->status(GDP_ERR_ARG, "gdp_described_count: bad argument");
+    GDP_HIP(w, hipSetDevice(c->device));
+    uint32_t n = 0;
+    GDP_HIP(w, hipMemcpyAsync(&n, w->d_count + b, sizeof n, hipMemcpyDeviceToHost, c->stream));
+    GDP_HIP(w, hipStreamSynchronize(c->stream));
+    *found = n;
+    return GDP_OK;
+} GDP_DESCRIBE_CATCH(w)
+
+int gdp_download_described(gdp_describe* w, int b, gdp_keypoint_described* host, size_t capacity, size_t* stored, size_t* found) try {
+    if (!w) return GDP_ERR_ARG;
+    const gdp_ctx* c = w->ctx;
+    if (b < 0 || b >= c->geom.batch || (!host && capacity)) return w->status(GDP_ERR_ARG, "gdp_download_described: bad argument");
+    if (stored) *stored = 0;
+    size_t total = 0;
+    const int rc = gdp_described_count(w, b, &total);
+    if (rc != GDP_OK) return rc;
+    if (found) *found = total;
+    const size_t n = std::min(total, std::min(w->capacity, capacity));
+    if (n == 0) return GDP_OK;
+    GDP_SETTLE(w, "gdp_download_described", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint_described)); });
+    GDP_HIP(w, hipMemcpyAsync(track_dma_ptr(host), w->d_out + (size_t)b * w->capacity, n * sizeof(gdp_keypoint_described),
+                              hipMemcpyDeviceToHost, c->stream));
+    GDP_HIP(w, hipStreamSynchronize(c->stream));
+    // the device order depends on the waves' timing, and two inputs may name the same sample: the
+    // position and the bin first, then the record's words, so equal keys are identical records
+    constexpr size_t kWords = sizeof(gdp_keypoint_described) / sizeof(uint32_t);
+    std::sort(host, host + n, [](const gdp_keypoint_described& p, const gdp_keypoint_described& q) {
+        if (p.octave != q.octave) return p.octave < q.octave;
+        if (p.scale != q.scale) return p.scale < q.scale;
+        if (p.row != q.row) return p.row < q.row;
+        if (p.col != q.col) return p.col < q.col;
+        if (p.bin != q.bin) return p.bin < q.bin;
+        uint32_t a[kWords], z[kWords];
+        std::memcpy(a, &p, sizeof a);
+        std::memcpy(z, &q, sizeof z);
+        return std::lexicographical_compare(a, a + kWords, z, z + kWords);
+    });
+    if (stored) *stored = n;
+    return GDP_OK;
+} GDP_DESCRIBE_CATCH(w)
+
+int gdp_device_described(const gdp_describe* w, int b, const gdp_keypoint_described** records, const uint32_t** count) try {
     if (!w || b < 0 || b >= w->ctx->geom.batch) return GDP_ERR_ARG;
     if (records) *records = w->d_out + (size_t)b * w->capacity;
     if (count) *count = w->d_count + b;

@@ -75,6 +75,12 @@ ORIENTED_DTYPE = np.dtype({"names": ["octave", "scale", "kind", "row", "col", "v
                            "offsets": [0, 2, 3, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44], "itemsize": 48})
 
 
+# struct gdp_keypoint_described (include/gdp.h): 176 bytes, the first 48 the input gdp_keypoint_oriented
+DESCRIBED_DTYPE = np.dtype({"names": list(ORIENTED_DTYPE.names) + ["desc"],
+                            "formats": [ORIENTED_DTYPE.fields[n][0] for n in ORIENTED_DTYPE.names] + [(np.uint8, (128,))],
+                            "offsets": [ORIENTED_DTYPE.fields[n][1] for n in ORIENTED_DTYPE.names] + [48], "itemsize": 176})
+
+
 class Keypoints(np.ndarray):
     """A KEYPOINT_DTYPE array of the stored records with `found`, the number the detection counted
     (larger than len() when the context's capacity was too small)."""
@@ -122,6 +128,17 @@ def orient_weights(S, scale):
     return t[:2 * r.value * r.value + 1].copy(), r.value
 
 
+def describe_tables(S, scale):
+    """(W[0:2R*R+1], R, C[0:1440], S[0:1440]): the descriptor window of `scale` in a pyramid of S —
+    W[d2] weighs a sample at squared distance d2 — and the quarter-degree rotation table
+    (gdp_describe_tables)."""
+    t = np.zeros(243, np.float32)
+    cos, sin = np.zeros(1440, np.float32), np.zeros(1440, np.float32)
+    r = _i()
+    check(lib().gdp_describe_tables(int(S), int(scale), _ptr(t), ctypes.byref(r), _ptr(cos), _ptr(sin)))
+    return t[:2 * r.value * r.value + 1].copy(), r.value, cos, sin
+
+
 class PyramidContext:
     """`batch` images of H x W int32 (or the row band [row_begin, row_end)) on one GPU.
 
@@ -150,6 +167,8 @@ class PyramidContext:
         self._kp_capacity = 65536  # gdp_set_keypoint_capacity's default
         self._orient = ctypes.c_void_p()  # the gdp_orient object, created on first use
         self._orient_capacity = 0         # 0: twice the keypoint capacity at creation
+        self._describe = ctypes.c_void_p()  # the gdp_describe object, created on first use
+        self._describe_capacity = 0         # 0: the orientation object's capacity
         self.input_format = "i32"
         if input_format != "i32":
             self.set_input_format(input_format)
@@ -529,6 +548,7 @@ class PyramidContext:
         return self._orient
 
     def _drop_orient(self):
+        self._drop_describe()  # it reads the orientation object at every launch: it goes first
         if getattr(self, "_orient", None) and self._orient.value:
             lib().gdp_orient_destroy(self._orient)
             self._orient = ctypes.c_void_p()
@@ -590,6 +610,84 @@ class PyramidContext:
         w = self._orient_handle()
         recs, count = ctypes.c_void_p(), ctypes.c_void_p()
         check(lib().gdp_device_oriented(w, int(b), ctypes.byref(recs), ctypes.byref(count)), w, orient=True)
+        return recs.value, count.value
+
+    # ------------------------------------------------------------------ descriptors (extension)
+    def _describe_handle(self):
+        """The context's gdp_describe object, created on first use from the context and its
+        orientation object (close() destroys it before both).  It only reads them: no call below
+        changes the pyramid or any of the three lists."""
+        if not self._describe.value:
+            src = self._orient_handle()
+            w = ctypes.c_void_p()
+            check(lib().gdp_describe_create(ctypes.byref(w), self._ctx, src, int(self._describe_capacity)), None, describe=True)
+            self._describe = w
+            self._describe_records = self._describe_capacity or self._orient_records  # what the object holds per image
+        return self._describe
+
+    def _drop_describe(self):
+        if getattr(self, "_describe", None) and self._describe.value:
+            lib().gdp_describe_destroy(self._describe)
+            self._describe = ctypes.c_void_p()
+
+    def set_describe_capacity(self, n):
+        """Described records kept per image, and the longest list set_describe_input takes (default:
+        the orientation capacity when the first descriptor call is made).  Drops the earlier results
+        and input lists."""
+        if int(n) <= 0:
+            raise ValueError("the descriptor capacity must be > 0")
+        self._drop_describe()
+        self._describe_capacity = int(n)
+
+    def set_describe_input(self, recs, b=0):
+        """Make `recs` (ORIENTED_DTYPE, or anything numpy converts to it) image b's descriptor input
+        instead of the oriented list (blocking; gdp_describe_set_input validates every record, the
+        angle's range included); None goes back to the oriented list."""
+        w = self._describe_handle()
+        if recs is None:
+            check(lib().gdp_describe_set_input(w, int(b), None, 0), w, describe=True)
+            return
+        recs = np.ascontiguousarray(recs, dtype=ORIENTED_DTYPE).reshape(-1)
+        keep = recs if recs.size else np.zeros(1, ORIENTED_DTYPE)  # an empty list is still a list: a non-null pointer
+        check(lib().gdp_describe_set_input(w, int(b), _ptr(keep), recs.size), w, describe=True)
+
+    def describe_keypoints(self, stream=None):
+        """Compute the 128-byte SIFT descriptor of every image's oriented list (the last
+        orient_keypoints', or set_describe_input's) on the CURRENT pyramid (gdp_describe_keypoints:
+        the Gaussian level rebuilt from levels s..S+2, a rotated 4 x 4 x 8 gradient histogram,
+        normalised, clipped at 0.2 and quantised); asynchronous on `stream`, one launch, no host read
+        of the counter."""
+        w = self._describe_handle()
+        check(lib().gdp_describe_keypoints(w, _stream_handle(stream)), w, describe=True)
+
+    def described_count(self, b=0):
+        """Records the last description produced for image b (blocking; may exceed the capacity)."""
+        if not self._describe.value:
+            return 0
+        n = ctypes.c_size_t()
+        check(lib().gdp_described_count(self._describe, int(b), ctypes.byref(n)), self._describe, describe=True)
+        return n.value
+
+    def described_keypoints(self, b=0):
+        """The stored records of image b as a DESCRIBED_DTYPE array sorted by (octave, scale, row,
+        col, bin) and then by the records' words (blocking); its `found` attribute is
+        described_count(b)."""
+        if not self._describe.value:
+            return np.zeros(0, DESCRIBED_DTYPE).view(Keypoints)
+        w = self._describe
+        out = np.zeros(min(self.described_count(b), self._describe_records), DESCRIBED_DTYPE)
+        stored, found = ctypes.c_size_t(), ctypes.c_size_t()
+        check(lib().gdp_download_described(w, int(b), _ptr(out) if out.size else None, out.size, ctypes.byref(stored),
+                                           ctypes.byref(found)), w, describe=True)
+        out = out[:stored.value].view(Keypoints)
+        out.found = found.value
+        return out
+
+    def device_described(self, b=0):
+        """(device address of image b's described records, device address of its uint32 counter)."""
+        w = self._describe_handle()
+        recs, count = ctypes.c_void_p(), ctypes.c_void_p()
+        check(lib().gdp_device_described(w, int(b), ctypes.byref(recs), ctypes.byref(count)), w, describe=True)
         return recs.value, count.value
 
     def device_level_ptr(self, b, o, s):
@@ -745,6 +843,14 @@ class GaussPyramid:
         self.SyncDevice()
         self._ctx.orient_keypoints()
         return self._ctx.oriented_keypoints(0)
+
+    def DescribeKeypoints(self):
+        """Extension: compute the SIFT descriptors of the last OrientKeypoints' records on the device
+        (PyramidContext.describe_keypoints) and return one DESCRIBED_DTYPE record per oriented
+        keypoint.  Host edits to GaussPy are described on; the pyramid is not changed."""
+        self.SyncDevice()
+        self._ctx.describe_keypoints()
+        return self._ctx.described_keypoints(0)
 
     def output(self, file=None):
         """:89-104 — print scale 0 of each octave (space separated) and an `==` separator row."""
