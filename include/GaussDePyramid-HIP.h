@@ -108,6 +108,15 @@ public:
     // clipped and quantised), sorted like gdp_download_described: one record per oriented record.
     // Pending host edits of GaussPy are uploaded first; the pyramid itself is not changed.
     std::vector<gdp_keypoint_described> DescribeKeypoints();
+    // Extension: match the last DescribeKeypoints' records of this pyramid (the queries) against
+    // those of `other` (the train side; it may be *this; same device) on the device
+    // (gdp_match_descriptors in gdp.h has the exact rule: exact squared L2 distances on the i8 matrix
+    // cores, nearest and second nearest with ties to the lowest index, Lowe's ratio test with `ratio`
+    // (0: off), a distance cap and the mutual test), sorted by `query` like gdp_download_matches.
+    // Indices name the lists in device order; qx, qy, tx, ty are the keypoints' image coordinates.
+    // Neither pyramid nor any list is changed; the match object lives for the call only.
+    std::vector<gdp_match_record> MatchDescriptors(GaussPyramid_hip& other, float ratio = 0.8f,
+                                                   uint32_t max_distance = 0xffffffffu, bool mutual = false);
     ~GaussPyramid_hip();
     bool initialized;
     bool mirror_host;  // GaussPy two-way: upload before / download after every mutating call (default true)
@@ -458,6 +467,31 @@ inline std::vector<gdp_keypoint_described> GaussPyramid_hip::DescribeKeypoints()
     std::vector<gdp_keypoint_described> out(found);
     check(gdp_describe_last_error(describe_), gdp_download_described(describe_, 0, out.data(), out.size(), &stored, nullptr));
     out.resize(stored);
+    return out;
+}
+
+inline std::vector<gdp_match_record> GaussPyramid_hip::MatchDescriptors(GaussPyramid_hip& other, float ratio, uint32_t max_distance,
+                                                                        bool mutual) {
+    auto check = [](const char* last, int status) {
+        if (status != GDP_OK) {
+            std::fprintf(stderr, "GaussPyramid_hip::MatchDescriptors failed: %s (%s)\n", gdp_status_string(status), last);
+            std::abort();
+        }
+    };
+    for (GaussPyramid_hip* g : {this, &other}) {  // a pyramid that was never described has an empty list
+        if (!g->orient_) check(gdp_orient_last_error(nullptr), gdp_orient_create(&g->orient_, g->ctx_, 0));
+        if (!g->describe_) check(gdp_describe_last_error(nullptr), gdp_describe_create(&g->describe_, g->ctx_, g->orient_, 0));
+    }
+    gdp_match* m = nullptr;
+    check(gdp_match_last_error(nullptr), gdp_match_create(&m, describe_, other.describe_, 0, 0));
+    // DescribeKeypoints ends in a blocking download, so nothing of `other` is still in flight on its stream
+    check(gdp_match_last_error(m), gdp_match_descriptors(m, 0, 0, ratio, max_distance, mutual ? 1 : 0, nullptr));
+    size_t found = 0, stored = 0;
+    check(gdp_match_last_error(m), gdp_match_count(m, &found));
+    std::vector<gdp_match_record> out(found);
+    check(gdp_match_last_error(m), gdp_download_matches(m, out.data(), out.size(), &stored, nullptr));
+    out.resize(stored);
+    gdp_match_destroy(m);
     return out;
 }
 

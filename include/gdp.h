@@ -543,6 +543,87 @@ int gdp_device_described(const gdp_describe* w, int b, const gdp_keypoint_descri
 int gdp_describe_tables(int S, int scale, float* weights /* 2R*R+1, at most 243 */, int* radius,
                         float* cos1440, float* sin1440);
 
+/* ---- extension: descriptor matching on the device ---------------------------------------------
+ * What the descriptors are for: the nearest and second-nearest TRAIN descriptor of every QUERY
+ * descriptor, brute force, where both lists already are (no reference counterpart, no parity claim).
+ * The distance sweep runs on the i8 matrix cores, which accumulate in int32, so every distance is an
+ * exact integer.  It writes nothing of a context, an orientation object or a describe object: its
+ * state is an object of its own, gdp_match, created from two const gdp_describe objects.
+ *
+ * The rule.  Integers only, apart from the two marked float steps, where every operation is a
+ * separately rounded float32 operation.  Two lists of gdp_keypoint_described records, the query
+ * list Q[0..nq) and the train list T[0..nt):
+ *   1 distance      dist(i, j) = sum over k < 128 of (Q[i].desc[k] - T[j].desc[k])^2, an exact
+ *                   integer (at most 128 * 255^2 = 8,323,200)
+ *   2 nearest       for query i the nearest train index is the j that minimises the pair
+ *                   (dist(i, j), j) lexicographically: ties go to the lowest index.  `distance` is
+ *                   its distance
+ *   3 second        `second` is the minimum of dist(i, j') over j' != j; it may equal `distance`.
+ *                   With nt = 1 it is 0xffffffff.  With nt = 0 the query yields nothing
+ *   4 ratio (float) when ratio != 0:  r2 = ratio * ratio (one rounded product);  keep when
+ *                   (float)distance < r2 * (float)second  (one rounded product, one comparison).
+ *                   (float)0xffffffff is 2^32; every real distance is below 2^24, so its conversion
+ *                   is exact
+ *   5 cap           keep when distance <= max_distance; 0xffffffff means no cap
+ *   6 mutual        when mutual != 0, keep only if i is the nearest query of train j under the same
+ *                   rule with the sides swapped: i minimises (dist(i', j), i') over i'
+ *   7 coordinates   (float) for a record, sc = (float)(1u << (octave & 31)),
+ *                   x = ((float)col + dcol) * sc,  y = ((float)row + drow) * sc
+ *   8 addresses     nothing is read from a record except octave, row, col, drow, dcol and desc, and
+ *                   no address is formed from record contents: any 176 bytes are a valid record
+ * At most one output record per query.  Every quantity is a function of the two lists with a total
+ * order for ties, so the result is an exact set, independent of tiling, chunking and wave timing.
+ * `query` and `train` index the lists in the order the kernel read them — the device order
+ * (gdp_device_described), which is unspecified for a list the pipeline produced and exactly the
+ * caller's for a list the caller supplied (gdp_match_set_input).  The coordinates are what a caller
+ * uses when they do not want to resolve indices. */
+typedef struct gdp_match_record {   /* 32 bytes, two 16-B stores */
+    uint32_t query, train;          /* indices into the lists as the kernel read them */
+    uint32_t distance, second;
+    float qx, qy, tx, ty;           /* image coordinates of the two keypoints */
+} gdp_match_record;
+typedef struct gdp_match gdp_match;
+/* A match object reading two describe objects (both non-NULL; they may be the same object, and may
+ * belong to different contexts, but must be on the same device, else GDP_ERR_ARG).  A capacity of 0
+ * means that object's capacity; neither may exceed 2^30.  The object owns an output buffer of
+ * query_capacity records, one uint32 counter, its scratch and the caller's lists.  Both describe
+ * objects are only read — looked up at every launch — and must outlive the match object: destroy it
+ * first.  gdp_match_last_error(m) describes m's last failure (m NULL: this thread's last failed
+ * create). */
+int gdp_match_create(gdp_match** out, const gdp_describe* query, const gdp_describe* train, size_t query_capacity,
+                     size_t train_capacity);
+void gdp_match_destroy(gdp_match* m);
+const char* gdp_match_last_error(const gdp_match* m);
+/* Make host[0..n) the list of `side` (0 query, 1 train) instead of the describe object's (blocking):
+ * n must not exceed that side's capacity, else GDP_ERR_ARG and nothing changes.  Records are not
+ * validated (point 8 of the rule).  An empty list (host non-NULL, n = 0) is a list; host = NULL goes
+ * back to the describe object's list. */
+int gdp_match_set_input(gdp_match* m, int side, const gdp_keypoint_described* host, size_t n);
+/* Match: zeroes the counter on `stream` (NULL = the QUERY context's own stream), then launches;
+ * asynchronous and stream-ordered.  When the train context's work runs on another stream the caller
+ * orders it.  A side without a list of the caller's reads the first min(counter, the describe
+ * object's capacity, that side's capacity) records of image query_image / train_image of its
+ * describe object; the count is read on the device, the host never reads it, so launching this right
+ * after gdp_describe_keypoints on the same stream is the normal use.  Outputs never exceed nq, so
+ * the buffer cannot overflow.  `ratio` is 0 (no ratio test) or in (0, 1]; a NaN or anything else is
+ * GDP_ERR_ARG, and so is an image index out of range.  The device order is unspecified. */
+int gdp_match_descriptors(gdp_match* m, int query_image, int train_image, float ratio, uint32_t max_distance,
+                          int mutual, void* stream);
+/* Records the last match produced (blocking; waits for the query context's OWN stream; 0 before any). */
+int gdp_match_count(gdp_match* m, size_t* found);
+/* Copy min(found, `capacity`) records to `host` (blocking), sorted ascending by `query`, which is
+ * unique per record.  *stored = records written, *found = gdp_match_count (either may be NULL). */
+int gdp_download_matches(gdp_match* m, gdp_match_record* host, size_t capacity, size_t* stored, size_t* found);
+/* Zero-copy view for device consumers: the records (query_capacity records, the first *count valid,
+ * device order) and the counter. */
+int gdp_device_matches(const gdp_match* m, const gdp_match_record** records, const uint32_t** count);
+/* How the object cuts the work (any output may be NULL): its two capacities; the chunk granule; and
+ * the number of chunks of the train list (one grid dimension of the distance sweep) and of the query
+ * list (the swapped sweep of the mutual test).  A list of n records in c chunks is cut at multiples of
+ * ceil(ceil(n / c) / granule) * granule, computed on the device from the count it reads. */
+int gdp_match_layout(const gdp_match* m, size_t* query_capacity, size_t* train_capacity, uint32_t* chunk_unit,
+                     uint32_t* train_chunks, uint32_t* query_chunks);
+
 /* ---- output --------------------------------------------------------------------------------
  * The blocking copies below are ordered after work on the context's OWN stream; if a build was
  * launched on another stream, synchronize that stream first. */

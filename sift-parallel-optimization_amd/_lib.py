@@ -145,6 +145,16 @@ SIGNATURES = {
     "gdp_download_described": (_c_int, [_p, _c_int, _p, _c_size, ctypes.POINTER(_c_size), ctypes.POINTER(_c_size)]),
     "gdp_device_described": (_c_int, [_p, _c_int, _pp, _pp]),
     "gdp_describe_tables": (_c_int, [_c_int, _c_int, _p, ctypes.POINTER(_c_int), _p, _p]),
+    "gdp_match_create": (_c_int, [_pp, _p, _p, _c_size, _c_size]),
+    "gdp_match_destroy": (None, [_p]),
+    "gdp_match_last_error": (ctypes.c_char_p, [_p]),
+    "gdp_match_set_input": (_c_int, [_p, _c_int, _p, _c_size]),
+    "gdp_match_descriptors": (_c_int, [_p, _c_int, _c_int, ctypes.c_float, _c_u32, _c_int, _p]),
+    "gdp_match_count": (_c_int, [_p, ctypes.POINTER(_c_size)]),
+    "gdp_download_matches": (_c_int, [_p, _p, _c_size, ctypes.POINTER(_c_size), ctypes.POINTER(_c_size)]),
+    "gdp_device_matches": (_c_int, [_p, _pp, _pp]),
+    "gdp_match_layout": (_c_int, [_p, ctypes.POINTER(_c_size), ctypes.POINTER(_c_size), ctypes.POINTER(_c_u32),
+                                  ctypes.POINTER(_c_u32), ctypes.POINTER(_c_u32)]),
     "gdp_checksum": (_c_int, [_p, _c_int, ctypes.POINTER(ctypes.c_uint64)]),
     "gdp_get_taps": (_c_int, [_p, _c_int, _c_int, _c_int, _p]),
     "gdp_set_window_centre": (_c_int, [_p, _c_int]),
@@ -207,12 +217,15 @@ def build_variants():
     return list(ids)
 
 
-def check(status, ctx=None, orient=False, describe=False):
+def check(status, ctx=None, orient=False, describe=False, match=False):
     """Raise GdpError for a non-zero status; `ctx` is the context whose gdp_last_error describes it
-    (orient=True: a gdp_orient object, or None for a failed gdp_orient_create; describe=True: the
-    same for a gdp_describe object)."""
+    (orient=True: a gdp_orient object, or None for a failed gdp_orient_create; describe=True and
+    match=True: the same for a gdp_describe and a gdp_match object)."""
     if status != GDP_OK:
         L = lib()
-        msg = L.gdp_describe_last_error(ctx) if describe else L.gdp_orient_last_error(ctx) if orient else L.gdp_last_error(ctx)
+        if match:
+            msg = L.gdp_match_last_error(ctx)
+        else:
+            msg = L.gdp_describe_last_error(ctx) if describe else L.gdp_orient_last_error(ctx) if orient else L.gdp_last_error(ctx)
         raise GdpError(status, (msg or b"").decode() or L.gdp_status_string(status).decode())
     return status

@@ -57,6 +57,7 @@ namespace {
 #include "gdp_refine.inc"
 #include "gdp_orient.inc"
 #include "gdp_describe.inc"
+#include "gdp_match.inc"
 #include "gdp_util.inc"
 #include "gdp_track.inc"
 
@@ -274,9 +275,37 @@ struct gdp_describe {
     }
 };
 
+// gdp_match_create: descriptor matching's state.  It reads two gdp_describe objects (looked up at
+// every launch, never written) and owns everything it writes: no export of it takes a mutable
+// context, orientation object or describe object.
+struct gdp_match {
+    const gdp_describe* side[2] = {nullptr, nullptr};  // 0 query, 1 train
+    int device = 0;                            // both sides' device
+    size_t cap[2] = {0, 0};                    // records a side may hold; cap[0] is also the output capacity
+    size_t pad[2] = {0, 0};                    // cap rounded up to kMaTile: the pitch of the scratch arrays
+    unsigned chunks[2] = {1, 1};               // [0]: chunks of the TRAIN list (queries on the lanes); [1]: the swapped pass
+    gdp_match_record* d_out = nullptr;         // [cap[0]]
+    uint32_t* d_count = nullptr;               // one counter
+    uint32_t* d_norm[2] = {nullptr, nullptr};  // [pad]: k_match_norm's norms
+    uint32_t* d_kb[2] = {nullptr, nullptr};    // [pad]: its packed key bases
+    uint4* d_part[2] = {nullptr, nullptr};     // [chunks[0]][pad[0]] and [chunks[1]][pad[1]] partial triples
+    gdp_keypoint_described* d_in[2] = {nullptr, nullptr};  // the caller's lists, allocated on first use
+    uint32_t* d_in_count = nullptr;            // [2]: their lengths; kMaNoList = the describe object's list
+    std::string err;
+    int status(int code, const char* fmt, ...) {
+        char buf[512];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(buf, sizeof buf, fmt, ap);
+        va_end(ap);
+        err = buf;
+        return code;
+    }
+};
+
 namespace {
 
-#define GDP_HIP(ctx, call)                                                                                   \
+#define GDP_HIP(ctx, call)                                                                                  \
     do {                                                                                                     \
         hipError_t e_ = (call);                                                                              \
         if (e_ != hipSuccess) return (ctx)->status(GDP_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_));    \
@@ -3414,6 +3443,211 @@ int gdp_device_described(const gdp_describe* w, int b, const gdp_keypoint_descri
     if (!w || b < 0 || b >= w->ctx->geom.batch) return GDP_ERR_ARG;
     if (records) *records = w->d_out + (size_t)b * w->capacity;
     if (count) *count = w->d_count + b;
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+// ---- extension: descriptor matching (gdp_match.inc) ------------------------------------------------
+// No export below takes a mutable context, orientation object or describe object: the state is the
+// gdp_match object's, the two describe objects are read (k_match_* take their lists const).
+static int match_exception(gdp_match* m, int code, const char* what) noexcept {
+    try {
+        if (m)
+            m->err = what;
+        else
+            g_create_error = what;
+    } catch (...) {
+    }
+    return code;
+}
+#define GDP_MATCH_CATCH(m)                                                                                    \
+    catch (const std::bad_alloc&) { return match_exception((m), GDP_ERR_NOMEM, "host allocation failed (std::bad_alloc)"); } \
+    catch (const std::exception& e_) { return match_exception((m), GDP_ERR_INTERNAL, e_.what()); }          \
+    catch (...) { return match_exception((m), GDP_ERR_INTERNAL, "unknown C++ exception"); }
+
+// chunks of the OTHER list for a pass whose lane axis holds `lanes_pad / kMaTile` tiles: enough for
+// kMaTargetWaves waves in the capacity grid, never shorter than kMaChunkUnit records
+static unsigned match_chunks(size_t lanes_pad, size_t other_cap) {
+    const size_t tiles = lanes_pad / kMaTile;
+    const size_t want = std::max<size_t>(1, (kMaTargetWaves + tiles - 1) / tiles);
+    const size_t most = std::max<size_t>(1, (other_cap + kMaChunkUnit - 1) / kMaChunkUnit);
+    return (unsigned)std::min(want, most);
+}
+
+void gdp_match_destroy(gdp_match* m) {
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    (void)hipDeviceSynchronize();  // a launch on any stream may still read or write the buffers
+    if (m->d_out) (void)hipFree(m->d_out);
+    if (m->d_count) (void)hipFree(m->d_count);
+    if (m->d_in_count) (void)hipFree(m->d_in_count);
+    for (int s = 0; s < 2; ++s) {
+        if (m->d_norm[s]) (void)hipFree(m->d_norm[s]);
+        if (m->d_kb[s]) (void)hipFree(m->d_kb[s]);
+        if (m->d_part[s]) (void)hipFree(m->d_part[s]);
+        if (m->d_in[s]) (void)hipFree(m->d_in[s]);
+    }
+    delete m;
+}
+
+int gdp_match_create(gdp_match** out, const gdp_describe* query, const gdp_describe* train, size_t query_capacity,
+                     size_t train_capacity) try {
+    if (!out || !query || !train) return GDP_ERR_ARG;
+    auto fail = [&](int code, const std::string& msg) {
+        g_create_error = msg;
+        return code;
+    };
+    if (query->ctx->device != train->ctx->device)
+        return fail(GDP_ERR_ARG, "gdp_match_create: the two describe objects are on different devices");
+    if (query_capacity == 0) query_capacity = query->capacity;
+    if (train_capacity == 0) train_capacity = train->capacity;
+    // indices and the counter are 32-bit, 0xffffffff is "none", and the grids are sized from these
+    if (query_capacity > (1ull << 30) || train_capacity > (1ull << 30))
+        return fail(GDP_ERR_ARG, "gdp_match_create: a capacity above 2^30 records");
+    hipError_t e = hipSetDevice(query->ctx->device);
+    if (e != hipSuccess) return fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    gdp_match* m = new gdp_match;
+    m->side[0] = query;
+    m->side[1] = train;
+    m->device = query->ctx->device;
+    m->cap[0] = query_capacity;
+    m->cap[1] = train_capacity;
+    for (int s = 0; s < 2; ++s) m->pad[s] = (size_t)round_up((long long)m->cap[s], kMaTile);
+    m->chunks[0] = match_chunks(m->pad[0], m->cap[1]);
+    m->chunks[1] = match_chunks(m->pad[1], m->cap[0]);
+    e = hipMalloc(reinterpret_cast<void**>(&m->d_out), m->cap[0] * sizeof(gdp_match_record));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_count), sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(m->d_count, 0, sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_in_count), 2 * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(m->d_in_count, 0xff, 2 * sizeof(uint32_t));  // kMaNoList
+    for (int s = 0; s < 2 && e == hipSuccess; ++s) {
+        e = hipMalloc(reinterpret_cast<void**>(&m->d_norm[s]), m->pad[s] * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_kb[s]), m->pad[s] * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_part[s]), m->chunks[s] * m->pad[s] * sizeof(uint4));
+    }
+    // hipMemset runs on the null stream, which the context's non-blocking stream does not wait for
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        const std::string msg = std::string("gdp_match_create (") + std::to_string(m->cap[0]) + " x " + std::to_string(m->cap[1]) +
+                                " records): " + hipGetErrorString(e);
+        gdp_match_destroy(m);
+        return fail(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, msg);
+    }
+    *out = m;
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+const char* gdp_match_last_error(const gdp_match* m) { return m ? m->err.c_str() : g_create_error.c_str(); }
+
+int gdp_match_layout(const gdp_match* m, size_t* query_capacity, size_t* train_capacity, uint32_t* chunk_unit,
+                     uint32_t* train_chunks, uint32_t* query_chunks) try {
+    if (!m) return GDP_ERR_ARG;
+    if (query_capacity) *query_capacity = m->cap[0];
+    if (train_capacity) *train_capacity = m->cap[1];
+    if (chunk_unit) *chunk_unit = kMaChunkUnit;
+    if (train_chunks) *train_chunks = m->chunks[0];
+    if (query_chunks) *query_chunks = m->chunks[1];
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+int gdp_match_set_input(gdp_match* m, int side, const gdp_keypoint_described* host, size_t n) try {
+    if (!m) return GDP_ERR_ARG;
+    if (side != 0 && side != 1) return m->status(GDP_ERR_ARG, "gdp_match_set_input: side is 0 (query) or 1 (train)");
+    if (host && n > m->cap[side])
+        return m->status(GDP_ERR_ARG, "gdp_match_set_input: %zu records exceed the capacity %zu", n, m->cap[side]);
+    GDP_HIP(m, hipSetDevice(m->device));
+    if (host && n) GDP_SETTLE(m, "gdp_match_set_input", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint_described)); });
+    if (host && !m->d_in[side]) {
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->d_in[side]), m->cap[side] * sizeof(gdp_keypoint_described));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            m->d_in[side] = nullptr;
+            return m->status(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, "gdp_match_set_input: input buffer: %s", hipGetErrorString(e));
+        }
+    }
+    // nothing is validated per record: the kernels read octave, row, col, drow, dcol and desc as data
+    // and form no address from them
+    hipStream_t st = m->side[0]->ctx->stream;
+    const uint32_t count = host ? (uint32_t)n : kMaNoList;
+    if (host && n)
+        GDP_HIP(m, hipMemcpyAsync(m->d_in[side], track_dma_ptr(host), n * sizeof(gdp_keypoint_described), hipMemcpyHostToDevice, st));
+    GDP_HIP(m, hipMemcpyAsync(m->d_in_count + side, &count, sizeof count, hipMemcpyHostToDevice, st));
+    GDP_HIP(m, hipStreamSynchronize(st));
+    return GDP_OK;
+} GDP_MATCH_CATCH(m)
+
+int gdp_match_descriptors(gdp_match* m, int query_image, int train_image, float ratio, uint32_t max_distance, int mutual,
+                          void* stream) try {
+    if (!m) return GDP_ERR_ARG;
+    if (!(ratio == 0.0f || (ratio > 0.0f && ratio <= 1.0f)))  // a NaN fails both
+        return m->status(GDP_ERR_ARG, "gdp_match_descriptors: ratio %g is neither 0 nor in (0, 1]", (double)ratio);
+    const int image[2] = {query_image, train_image};
+    MaSide sd[2];
+    for (int s = 0; s < 2; ++s) {
+        const gdp_describe* d = m->side[s];
+        if (image[s] < 0 || image[s] >= d->ctx->geom.batch)
+            return m->status(GDP_ERR_ARG, "gdp_match_descriptors: %s image %d of %d", s ? "train" : "query", image[s], d->ctx->geom.batch);
+        sd[s].src = reinterpret_cast<const char*>(d->d_out + (size_t)image[s] * d->capacity);
+        sd[s].src_count = d->d_count + image[s];
+        sd[s].src_cap = (unsigned)std::min<size_t>(std::min(d->capacity, m->cap[s]), 1u << 30);
+        sd[s].own = reinterpret_cast<const char*>(m->d_in[s]);
+        sd[s].own_count = m->d_in_count + s;
+    }
+    GDP_HIP(m, hipSetDevice(m->device));
+    hipStream_t st = m->side[0]->ctx->pick(stream);
+    const float r2 = ratio * ratio;  // one rounded float32 product
+    GDP_HIP(m, hipMemsetAsync(m->d_count, 0, sizeof(uint32_t), st));
+    const size_t longest = std::max(m->cap[0], m->cap[1]);
+    hipLaunchKernelGGL(k_match_norm, dim3((unsigned)((longest + 255) / 256), 2), dim3(256), 0, st, sd[0], sd[1], m->d_norm[0],
+                       m->d_kb[0], m->d_norm[1], m->d_kb[1]);
+    for (int pass = 0; pass < (mutual ? 2 : 1); ++pass) {  // pass 1: the sides swapped
+        const int q = pass, t = 1 - pass;
+        const size_t tiles = m->pad[q] / kMaTile;
+        hipLaunchKernelGGL(k_match_nn, dim3((unsigned)((tiles + kMaWaves - 1) / kMaWaves), m->chunks[pass]), dim3(kMaBlock), 0, st,
+                           sd[q], sd[t], m->d_norm[q], m->d_kb[t], m->d_part[pass], (unsigned)m->pad[q], m->chunks[pass]);
+    }
+    hipLaunchKernelGGL(k_match_select, dim3((unsigned)((m->cap[0] + 255) / 256)), dim3(256), 0, st, sd[0], sd[1], m->d_part[0],
+                       (unsigned)m->pad[0], m->chunks[0], m->d_part[1], (unsigned)m->pad[1], m->chunks[1], ratio != 0.0f ? 1 : 0, r2,
+                       max_distance, mutual ? 1 : 0, reinterpret_cast<uint4*>(m->d_out), m->d_count);
+    GDP_HIP(m, hipGetLastError());
+    return GDP_OK;
+} GDP_MATCH_CATCH(m)
+
+int gdp_match_count(gdp_match* m, size_t* found) try {
+    if (!m || !found) return m ? m->status(GDP_ERR_ARG, "gdp_match_count: bad argument") : GDP_ERR_ARG;
+    GDP_HIP(m, hipSetDevice(m->device));
+    hipStream_t st = m->side[0]->ctx->stream;
+    uint32_t n = 0;
+    GDP_HIP(m, hipMemcpyAsync(&n, m->d_count, sizeof n, hipMemcpyDeviceToHost, st));
+    GDP_HIP(m, hipStreamSynchronize(st));
+    *found = n;
+    return GDP_OK;
+} GDP_MATCH_CATCH(m)
+
+int gdp_download_matches(gdp_match* m, gdp_match_record* host, size_t capacity, size_t* stored, size_t* found) try {
+    if (!m) return GDP_ERR_ARG;
+    if (!host && capacity) return m->status(GDP_ERR_ARG, "gdp_download_matches: bad argument");
+    if (stored) *stored = 0;
+    size_t total = 0;
+    const int rc = gdp_match_count(m, &total);
+    if (rc != GDP_OK) return rc;
+    if (found) *found = total;
+    const size_t n = std::min(total, std::min(m->cap[0], capacity));
+    if (n == 0) return GDP_OK;
+    hipStream_t st = m->side[0]->ctx->stream;
+    GDP_SETTLE(m, "gdp_download_matches", [&](auto&& f) { f(host, n * sizeof(gdp_match_record)); });
+    GDP_HIP(m, hipMemcpyAsync(track_dma_ptr(host), m->d_out, n * sizeof(gdp_match_record), hipMemcpyDeviceToHost, st));
+    GDP_HIP(m, hipStreamSynchronize(st));
+    // the device order depends on the waves' timing; a query yields at most one record
+    std::sort(host, host + n, [](const gdp_match_record& p, const gdp_match_record& q) { return p.query < q.query; });
+    if (stored) *stored = n;
+    return GDP_OK;
+} GDP_MATCH_CATCH(m)
+
+int gdp_device_matches(const gdp_match* m, const gdp_match_record** records, const uint32_t** count) try {
+    if (!m) return GDP_ERR_ARG;
+    if (records) *records = m->d_out;
+    if (count) *count = m->d_count;
     return GDP_OK;
 } GDP_ABI_CATCH(nullptr)
 

@@ -42,6 +42,7 @@ row band), used by bench.py and the multi-GPU driver.
 """
 import ctypes
 import sys
+import weakref
 
 import numpy as np
 
@@ -79,6 +80,12 @@ ORIENTED_DTYPE = np.dtype({"names": ["octave", "scale", "kind", "row", "col", "v
 DESCRIBED_DTYPE = np.dtype({"names": list(ORIENTED_DTYPE.names) + ["desc"],
                             "formats": [ORIENTED_DTYPE.fields[n][0] for n in ORIENTED_DTYPE.names] + [(np.uint8, (128,))],
                             "offsets": [ORIENTED_DTYPE.fields[n][1] for n in ORIENTED_DTYPE.names] + [48], "itemsize": 176})
+
+
+# struct gdp_match_record (include/gdp.h): 32 bytes
+MATCH_DTYPE = np.dtype({"names": ["query", "train", "distance", "second", "qx", "qy", "tx", "ty"],
+                        "formats": [np.uint32, np.uint32, np.uint32, np.uint32, np.float32, np.float32, np.float32, np.float32],
+                        "offsets": [0, 4, 8, 12, 16, 20, 24, 28], "itemsize": 32})
 
 
 class Keypoints(np.ndarray):
@@ -626,6 +633,11 @@ class PyramidContext:
         return self._describe
 
     def _drop_describe(self):
+        # every match object that reads this describe object goes first: this context's own, and
+        # those of the contexts that match against this one as their train side
+        self._drop_match()
+        for reader in list(getattr(self, "_match_readers", ())):
+            reader._drop_match()
         if getattr(self, "_describe", None) and self._describe.value:
             lib().gdp_describe_destroy(self._describe)
             self._describe = ctypes.c_void_p()
@@ -689,6 +701,109 @@ class PyramidContext:
         recs, count = ctypes.c_void_p(), ctypes.c_void_p()
         check(lib().gdp_device_described(w, int(b), ctypes.byref(recs), ctypes.byref(count)), w, describe=True)
         return recs.value, count.value
+
+    # ------------------------------------------------------------------ descriptor matching (extension)
+    def _match_handle(self, train=None):
+        """The gdp_match object that reads this context's describe object (query side) and
+        `train`'s (None: this context's), created on first use and again when `train` changes.  It
+        only reads the two describe objects and is dropped before either of them."""
+        train = self if train is None else train
+        m = getattr(self, "_match", None)
+        if m is not None and m.value and self._match_train() is train:
+            return m
+        self._drop_match()
+        q, t = self._describe_handle(), train._describe_handle()
+        m = ctypes.c_void_p()
+        qcap, tcap = getattr(self, "_match_capacity", (0, 0))
+        check(lib().gdp_match_create(ctypes.byref(m), q, t, int(qcap), int(tcap)), None, match=True)
+        self._match = m
+        self._match_train = weakref.ref(train)
+        if not hasattr(train, "_match_readers"):
+            train._match_readers = weakref.WeakSet()
+        train._match_readers.add(self)
+        return m
+
+    def _match_current(self):
+        """The match object as last created (its train side kept), or a new one against this context."""
+        m = getattr(self, "_match", None)
+        return self._match_handle(self._match_train() if m is not None and m.value else None)
+
+    def _drop_match(self):
+        m = getattr(self, "_match", None)
+        if m is not None and m.value:
+            lib().gdp_match_destroy(m)
+            self._match = ctypes.c_void_p()
+
+    def set_match_capacity(self, query=0, train=0):
+        """Records the match object holds per side (0: that side's descriptor capacity); the query
+        capacity is also the most matches kept.  Drops the earlier results and input lists."""
+        if int(query) < 0 or int(train) < 0:
+            raise ValueError("a match capacity must be >= 0")
+        self._drop_match()
+        self._match_capacity = (int(query), int(train))
+
+    def match_descriptors(self, train=None, query_image=0, train_image=0, ratio=0.8, max_distance=None, mutual=False, stream=None):
+        """Match image `query_image`'s described list of this context against image `train_image`'s
+        of `train` (another PyramidContext on the same device, None: this one) on the device
+        (gdp_match_descriptors: exact nearest and second-nearest by squared L2 distance on the i8
+        matrix cores, ties to the lowest index; Lowe's ratio test with `ratio` (0: off), a distance
+        cap and the mutual test); asynchronous on `stream`, no host read of either counter."""
+        m = self._match_handle(train)
+        cap = 0xffffffff if max_distance is None else int(max_distance)
+        check(lib().gdp_match_descriptors(m, int(query_image), int(train_image), float(ratio), cap, int(bool(mutual)),
+                                          _stream_handle(stream)), m, match=True)
+
+    def set_match_input(self, side, recs):
+        """Make `recs` (DESCRIBED_DTYPE) the list of `side` (0 query, 1 train) instead of the
+        describe object's (blocking; records are not validated: any 176 bytes are a record); None
+        goes back to the describe object's list."""
+        m = self._match_current()
+        if recs is None:
+            check(lib().gdp_match_set_input(m, int(side), None, 0), m, match=True)
+            return
+        recs = np.ascontiguousarray(recs, dtype=DESCRIBED_DTYPE).reshape(-1)
+        keep = recs if recs.size else np.zeros(1, DESCRIBED_DTYPE)  # an empty list is still a list: a non-null pointer
+        check(lib().gdp_match_set_input(m, int(side), _ptr(keep), recs.size), m, match=True)
+
+    def match_count(self):
+        """Records the last match produced (blocking; 0 before any)."""
+        m = getattr(self, "_match", None)
+        if m is None or not m.value:
+            return 0
+        n = ctypes.c_size_t()
+        check(lib().gdp_match_count(m, ctypes.byref(n)), m, match=True)
+        return n.value
+
+    def matches(self):
+        """The last match's records as a MATCH_DTYPE array sorted by `query` (blocking); its `found`
+        attribute is match_count()."""
+        m = getattr(self, "_match", None)
+        if m is None or not m.value:
+            return np.zeros(0, MATCH_DTYPE).view(Keypoints)
+        out = np.zeros(self.match_count(), MATCH_DTYPE)
+        stored, found = ctypes.c_size_t(), ctypes.c_size_t()
+        check(lib().gdp_download_matches(m, _ptr(out) if out.size else None, out.size, ctypes.byref(stored), ctypes.byref(found)),
+              m, match=True)
+        out = out[:stored.value].view(Keypoints)
+        out.found = found.value
+        return out
+
+    def device_matches(self):
+        """(device address of the match records, device address of their uint32 counter)."""
+        m = self._match_current()
+        recs, count = ctypes.c_void_p(), ctypes.c_void_p()
+        check(lib().gdp_device_matches(m, ctypes.byref(recs), ctypes.byref(count)), m, match=True)
+        return recs.value, count.value
+
+    def match_layout(self):
+        """(query capacity, train capacity, chunk granule, train chunks, query chunks) of the match
+        object (gdp_match_layout)."""
+        m = self._match_current()
+        qc, tc = ctypes.c_size_t(), ctypes.c_size_t()
+        unit, tch, qch = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        check(lib().gdp_match_layout(m, ctypes.byref(qc), ctypes.byref(tc), ctypes.byref(unit), ctypes.byref(tch), ctypes.byref(qch)),
+              m, match=True)
+        return qc.value, tc.value, unit.value, tch.value, qch.value
 
     def device_level_ptr(self, b, o, s):
         """Device address of level (o, s) of image b.  Read-only: after writing through it, call
@@ -851,6 +966,14 @@ class GaussPyramid:
         self.SyncDevice()
         self._ctx.describe_keypoints()
         return self._ctx.described_keypoints(0)
+
+    def MatchDescriptors(self, other=None, ratio=0.8, max_distance=None, mutual=False):
+        """Extension: match the last DescribeKeypoints' records of this pyramid (the queries) against
+        those of `other` (another GaussPyramid on the same device; None: this one) on the device
+        (PyramidContext.match_descriptors) and return the MATCH_DTYPE records sorted by `query`.
+        Neither pyramid nor any list is changed."""
+        self._ctx.match_descriptors(None if other is None else other._ctx, 0, 0, ratio, max_distance, mutual)
+        return self._ctx.matches()
 
     def output(self, file=None):
         """:89-104 — print scale 0 of each octave (space separated) and an `==` separator row."""
