@@ -27,6 +27,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <type_traits>
 #include <utility>
 #include <array>
@@ -110,9 +111,24 @@ const char* exp_env(const char*) { return nullptr; }
 
 thread_local std::string g_create_error;
 
+// The error state of every handle (context, orientation, describe and match objects): the text
+// behind its *_last_error export.  A NULL handle's errors go to g_create_error instead.
+struct ErrorState {
+    std::string err;
+    int status(int code, const char* fmt, ...) {
+        char buf[512];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(buf, sizeof buf, fmt, ap);
+        va_end(ap);
+        err = buf;
+        return code;
+    }
+};
+
 }  // namespace
 
-struct gdp_ctx {
+struct gdp_ctx : ErrorState {
     int device = 0;
     Geom geom{};
     Geom* d_geom = nullptr;
@@ -208,16 +224,6 @@ struct gdp_ctx {
     int inplace_sub = 1;          // GDP_TUNE_INPLACE_SUB: k_levels blocks per 1024-group chunk (1, 2, 4)
     int window_sub = 4;           // GDP_TUNE_WINDOW_SUB: k_window blocks per chunk (4 = 256-thread blocks:
                                   // 6.7 vs 5.9 TB/s at 4096^2, tools/tune.py)
-    std::string err;
-    int status(int code, const char* fmt, ...) {
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        err = buf;
-        return code;
-    }
     // NULL = the context's own stream; GDP_STREAM_NULL ((void*)1) = HIP's default (null) stream
     hipStream_t pick(void* s) const {
         if (s == GDP_STREAM_NULL) return (hipStream_t)0;
@@ -228,7 +234,7 @@ struct gdp_ctx {
 // gdp_orient_create: orientation assignment's state.  It lives outside the context on purpose: the
 // orientation only READS the context (pyramid, geometry, refined list — all looked up at launch
 // time), so no export of it takes a mutable gdp_ctx* and the build that follows stays a kept one.
-struct gdp_orient {
+struct gdp_orient : ErrorState {
     const gdp_ctx* ctx = nullptr;
     size_t capacity = 0;                   // oriented records kept per image; also the longest list of the caller's
     float* d_weights = nullptr;            // [S][kOrWeights]: w_s[d2] of scale s at (s - 1) * kOrWeights
@@ -237,22 +243,12 @@ struct gdp_orient {
     gdp_keypoint_refined* d_in = nullptr;  // [batch][capacity]: the caller's lists, allocated on first use
     uint32_t* d_in_count = nullptr;        // [batch]: their lengths; kOrNoList = the context's refined list
     std::vector<uint32_t> in_count;        // host copy of d_in_count
-    std::string err;
-    int status(int code, const char* fmt, ...) {
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        err = buf;
-        return code;
-    }
 };
 
 // gdp_describe_create: the descriptors' state.  Like gdp_orient it lives outside the context, and
 // outside the orientation object too: k_describe only READS the pyramid, the geometry and the
 // oriented list (all looked up at launch time), so no export of it takes a mutable gdp_ctx*.
-struct gdp_describe {
+struct gdp_describe : ErrorState {
     const gdp_ctx* ctx = nullptr;
     const gdp_orient* src = nullptr;         // whose oriented list is described; NULL: the caller's lists only
     size_t capacity = 0;                     // described records kept per image; also the longest list of the caller's
@@ -263,22 +259,12 @@ struct gdp_describe {
     gdp_keypoint_oriented* d_in = nullptr;   // [batch][capacity]: the caller's lists, allocated on first use
     uint32_t* d_in_count = nullptr;          // [batch]: their lengths; kDeNoList = src's list
     std::vector<uint32_t> in_count;          // host copy of d_in_count
-    std::string err;
-    int status(int code, const char* fmt, ...) {
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        err = buf;
-        return code;
-    }
 };
 
 // gdp_match_create: descriptor matching's state.  It reads two gdp_describe objects (looked up at
 // every launch, never written) and owns everything it writes: no export of it takes a mutable
 // context, orientation object or describe object.
-struct gdp_match {
+struct gdp_match : ErrorState {
     const gdp_describe* side[2] = {nullptr, nullptr};  // 0 query, 1 train
     int device = 0;                            // both sides' device
     size_t cap[2] = {0, 0};                    // records a side may hold; cap[0] is also the output capacity
@@ -291,16 +277,6 @@ struct gdp_match {
     uint4* d_part[2] = {nullptr, nullptr};     // [chunks[0]][pad[0]] and [chunks[1]][pad[1]] partial triples
     gdp_keypoint_described* d_in[2] = {nullptr, nullptr};  // the caller's lists, allocated on first use
     uint32_t* d_in_count = nullptr;            // [2]: their lengths; kMaNoList = the describe object's list
-    std::string err;
-    int status(int code, const char* fmt, ...) {
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        err = buf;
-        return code;
-    }
 };
 
 namespace {
@@ -745,24 +721,24 @@ hipError_t launch_conv_sweep_l(gdp_ctx* c, unsigned grid, hipStream_t st) {
 }
 
 // ---- no C++ exception crosses the C ABI --------------------------------------------------------
-// Every int-returning export is a function-try-block ending in GDP_ABI_CATCH(ctx): std::bad_alloc
-// becomes GDP_ERR_NOMEM, anything else GDP_ERR_INTERNAL, with the text in gdp_last_error(ctx)
-// (ctx NULL: the thread's create error).  The exports that return pointers / sizes / void do not
-// allocate.
-static int abi_exception(const gdp_ctx* c, int code, const char* what) noexcept {
+// Every int-returning export is a function-try-block ending in GDP_ABI_CATCH(handle): std::bad_alloc
+// becomes GDP_ERR_NOMEM, anything else GDP_ERR_INTERNAL, with the text in the handle's *_last_error
+// (a context, an orientation, describe or match object; NULL: the thread's create error).  The
+// exports that return pointers / sizes / void do not allocate.
+static int abi_exception(const ErrorState* h, int code, const char* what) noexcept {
     try {
-        if (c)
-            const_cast<gdp_ctx*>(c)->err = what;
+        if (h)
+            const_cast<ErrorState*>(h)->err = what;
         else
             g_create_error = what;
     } catch (...) {
     }
     return code;
 }
-#define GDP_ABI_CATCH(ctx)                                                                                   \
-    catch (const std::bad_alloc&) { return abi_exception((ctx), GDP_ERR_NOMEM, "host allocation failed (std::bad_alloc)"); } \
-    catch (const std::exception& e_) { return abi_exception((ctx), GDP_ERR_INTERNAL, e_.what()); }         \
-    catch (...) { return abi_exception((ctx), GDP_ERR_INTERNAL, "unknown C++ exception"); }
+#define GDP_ABI_CATCH(h)                                                                                     \
+    catch (const std::bad_alloc&) { return abi_exception((h), GDP_ERR_NOMEM, "host allocation failed (std::bad_alloc)"); } \
+    catch (const std::exception& e_) { return abi_exception((h), GDP_ERR_INTERNAL, e_.what()); }           \
+    catch (...) { return abi_exception((h), GDP_ERR_INTERNAL, "unknown C++ exception"); }
 
 // Deferred mirrors overlapping the caller host memory an entry is given are completed first: no
 // libgdp copy may fault on a stale page (gdp_track.inc).  `ranges(f)` calls f(ptr, bytes) for
@@ -789,6 +765,243 @@ static int settle_deferred(C* c, const char* what, F&& ranges) {
         const int settle_rc_ = settle_deferred((c), (what), __VA_ARGS__); \
         if (settle_rc_ != GDP_OK) return settle_rc_;                      \
     } while (0)
+
+// ---- the keypoint stages' host layer ---------------------------------------------------------------
+// Extrema and refinement keep their lists in the context; orientation, descriptors and matching in
+// objects of their own (H below: any of the four handles).  What they share is here, once.
+namespace {
+
+// the context whose device and stream a handle's copies and counter reads use (matching: the query side's)
+const gdp_ctx* ctx_of(const gdp_ctx* c) { return c; }
+const gdp_ctx* ctx_of(const gdp_orient* w) { return w->ctx; }
+const gdp_ctx* ctx_of(const gdp_describe* w) { return w->ctx; }
+const gdp_ctx* ctx_of(const gdp_match* m) { return m->side[0]->ctx; }
+
+// d_in_count of a slot that reads its producer's list, not the caller's
+constexpr uint32_t kNoList = 0xffffffffu;
+static_assert(kOrNoList == kNoList && kDeNoList == kNoList && kMaNoList == kNoList, "one sentinel, filled bytewise (0xff)");
+
+// element i of a device array that may not be allocated yet
+template <class T>
+T* at(T* p, size_t i) {
+    return p ? p + i : nullptr;
+}
+
+int create_fail(int code, const std::string& m) {
+    g_create_error = m;
+    return code;
+}
+
+// A row band does not hold the neighbourhoods of the samples near its edges: "" on a whole-image context
+std::string row_band_error(const Geom& g, const char* who, const char* missing, const char* verb) {
+    if (g.in_row0 == 0 && g.in_rows == g.H) return std::string();
+    return std::string(who) + ": a row band does not hold its " + missing + " across the band edges; " + verb +
+           " on a whole-image context";
+}
+
+int check_thresholds(gdp_ctx* c, const char* who, float contrast_threshold, float edge_ratio) {
+    if (!(contrast_threshold >= 0.0f)) return c->status(GDP_ERR_ARG, "%s: contrast_threshold must be >= 0", who);
+    if (edge_ratio != 0.0f && !(edge_ratio >= 1.0f && std::isfinite(edge_ratio)))
+        return c->status(GDP_ERR_ARG, "%s: edge_ratio must be 0 (no edge test) or finite and >= 1", who);
+    return GDP_OK;
+}
+
+// The record names an interior sample of a candidate level of this context: exactly what k_refine,
+// k_orient and k_describe check before they form an address from it.
+template <class R>
+bool names_sample(const Geom& g, const R& k) {
+    return (int)k.octave < g.O && k.scale >= 1 && (int)k.scale <= g.S && k.row >= 1 && k.row <= g.oct[k.octave].rows - 2 &&
+           k.col >= 1 && k.col <= g.oct[k.octave].cols - 2;
+}
+
+// n counters filled bytewise.  hipMemset runs on the null stream, which a context's non-blocking
+// stream does not wait for: the fill must have landed before a launch on that stream counts into
+// the buffer or reads it.
+hipError_t alloc_counters(uint32_t** count, size_t n, int byte) {
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(count), n * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(*count, byte, n * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    return e;
+}
+
+// A stage's output: `records` records and n zeroed counters, whichever of the two is not there yet
+template <class R>
+hipError_t alloc_list(R** list, size_t records, uint32_t** count, size_t n) {
+    hipError_t e = hipSuccess;
+    if (!*list) e = hipMalloc(reinterpret_cast<void**>(list), records * sizeof(R));
+    if (e == hipSuccess && !*count) e = alloc_counters(count, n, 0);
+    return e;
+}
+
+// The context's own lists, [batch][kp_capacity] records and [batch] counters, allocated on first use
+template <class R>
+int ensure_list(gdp_ctx* c, R** list, uint32_t** count, const char* what) {
+    if (*list && *count) return GDP_OK;
+    const size_t batch = (size_t)c->geom.batch;
+    const hipError_t e = c->kp_capacity > (SIZE_MAX / sizeof(R)) / batch ? hipErrorOutOfMemory
+                                                                          : alloc_list(list, c->kp_capacity * batch, count, batch);
+    if (e == hipSuccess) return GDP_OK;
+    (void)hipGetLastError();
+    return c->status(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, "%s (%zu records x %zu images): %s", what,
+                     c->kp_capacity, batch, hipGetErrorString(e));
+}
+int ensure_keypoints(gdp_ctx* c) { return ensure_list(c, &c->d_kp, &c->d_kp_count, "keypoint buffer"); }
+int ensure_refined(gdp_ctx* c) { return ensure_list(c, &c->d_rf, &c->d_rf_count, "refined keypoint buffer"); }
+
+hipError_t upload_table(float** d_table, const std::vector<float>& table) {
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(d_table), table.size() * sizeof(float));
+    return e != hipSuccess ? e : hipMemcpy(*d_table, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice);
+}
+
+// A *_create that failed on the device: the object goes, the thread's create error says why
+template <class W>
+int create_failed(W* w, void (*destroy)(W*), const std::string& what, hipError_t e) {
+    (void)hipGetLastError();
+    const std::string m = what + hipGetErrorString(e);
+    destroy(w);
+    return create_fail(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, m);
+}
+
+// The end of gdp_orient_create and gdp_describe_create, `e` being what the tables' upload returned:
+// the output list with its counters and the input lists' counters (all on the producer's list)
+template <class W>
+int finish_create(W** out, W* w, void (*destroy)(W*), const char* who, size_t batch, hipError_t e) {
+    if (e == hipSuccess) e = alloc_list(&w->d_out, w->capacity * batch, &w->d_count, batch);
+    if (e == hipSuccess) e = alloc_counters(&w->d_in_count, batch, 0xff);  // kNoList
+    if (e != hipSuccess)
+        return create_failed(w, destroy, std::string(who) + " (" + std::to_string(w->capacity) + " records x " +
+                                             std::to_string(batch) + " images): ", e);
+    *out = w;
+    return GDP_OK;
+}
+
+// One counter; 0 while the stage that owns it has not allocated it
+template <class H>
+int read_counter(H* h, const uint32_t* d_count, size_t* out) {
+    *out = 0;
+    if (!d_count) return GDP_OK;
+    const gdp_ctx* c = ctx_of(h);
+    GDP_HIP(h, hipSetDevice(c->device));
+    uint32_t n = 0;
+    GDP_HIP(h, hipMemcpyAsync(&n, d_count, sizeof n, hipMemcpyDeviceToHost, c->stream));
+    GDP_HIP(h, hipStreamSynchronize(c->stream));
+    *out = n;
+    return GDP_OK;
+}
+
+// The downloads' orders: the device order depends on the waves' timing.
+template <class R>
+auto sample_of(const R& k) {
+    return std::make_tuple(k.octave, k.scale, k.row, k.col);
+}
+// detected: (octave, scale, row, col) is unique per record
+bool record_less(const gdp_keypoint& p, const gdp_keypoint& q) { return sample_of(p) < sample_of(q); }
+// refined: two inputs may end at the same sample: the position first, then the bits of everything
+// else, so equal keys are identical records
+bool record_less(const gdp_keypoint_refined& p, const gdp_keypoint_refined& q) {
+    auto bits = [](float f) {
+        uint32_t u;
+        std::memcpy(&u, &f, sizeof u);
+        return u;
+    };
+    auto key = [&](const gdp_keypoint_refined& k) {
+        return std::tuple_cat(sample_of(k), std::make_tuple(bits(k.dscale), bits(k.drow), bits(k.dcol), bits(k.interp),
+                                                            bits(k.value), (uint8_t)k.kind));
+    };
+    return key(p) < key(q);
+}
+// oriented and described: two inputs may name the same sample: the position and the bin first, then
+// the record's words, so equal keys are identical records
+template <class R>
+bool record_less(const R& p, const R& q) {
+    const auto kp = std::tuple_cat(sample_of(p), std::make_tuple(p.bin)), kq = std::tuple_cat(sample_of(q), std::make_tuple(q.bin));
+    if (kp != kq) return kp < kq;
+    constexpr size_t kWords = sizeof(R) / sizeof(uint32_t);
+    uint32_t a[kWords], z[kWords];
+    std::memcpy(a, &p, sizeof a);
+    std::memcpy(z, &q, sizeof z);
+    return std::lexicographical_compare(a, a + kWords, z, z + kWords);
+}
+// matches: a query yields at most one record
+bool record_less(const gdp_match_record& p, const gdp_match_record& q) { return p.query < q.query; }
+
+// One list into the caller's buffer, in record_less order: *found the list's count, *stored how many of
+// them fit (both optional).  d_list / d_count NULL: the stage has not run, nothing is stored.
+template <class H, class R>
+int download_sorted(H* h, const char* who, const R* d_list, const uint32_t* d_count, size_t list_capacity, R* host,
+                    size_t capacity, size_t* stored, size_t* found) {
+    if (stored) *stored = 0;
+    size_t total = 0;
+    const int rc = read_counter(h, d_count, &total);
+    if (rc != GDP_OK) return rc;
+    if (found) *found = total;
+    const size_t have = std::min(total, list_capacity), n = std::min(have, capacity);
+    if (n == 0 || !d_list) return GDP_OK;
+    GDP_SETTLE(h, who, [&](auto&& f) { f(host, n * sizeof(R)); });
+    // a buffer shorter than the list takes the head of the SORTED list, the same run to run (the head of
+    // the device order would not be): the whole list is sorted in a host copy first
+    std::vector<R> whole(n < have ? have : 0);
+    R* const dst = n < have ? whole.data() : host;
+    const hipStream_t st = ctx_of(h)->stream;
+    GDP_HIP(h, hipMemcpyAsync(n < have ? dst : track_dma_ptr(host), d_list, have * sizeof(R), hipMemcpyDeviceToHost, st));
+    GDP_HIP(h, hipStreamSynchronize(st));
+    std::sort(dst, dst + have, [](const R& p, const R& q) { return record_less(p, q); });
+    if (n < have) std::copy_n(dst, n, host);
+    if (stored) *stored = n;
+    return GDP_OK;
+}
+
+// Replaces one input list of a stage (the capacity is the caller's check).  host NULL: the slot reads
+// its producer's list again; else its n records (0: an empty list), each accepted by check(i, record)
+// returning GDP_OK, go to *d_in + offset — *d_in holds `records` of them, allocated on first use.
+template <class H, class R, class Check>
+int replace_input(H* h, const char* who, R** d_in, size_t records, size_t offset, uint32_t* d_count, const R* host, size_t n,
+                  Check&& check) {
+    const gdp_ctx* c = ctx_of(h);
+    GDP_HIP(h, hipSetDevice(c->device));
+    if (host && n) GDP_SETTLE(h, who, [&](auto&& f) { f(host, n * sizeof(R)); });
+    for (size_t i = 0; host && i < n; ++i) {
+        const int rc = check(i, host[i]);
+        if (rc != GDP_OK) return rc;
+    }
+    if (host && !*d_in) {
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(d_in), records * sizeof(R));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            *d_in = nullptr;
+            return h->status(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, "%s: input buffer: %s", who, hipGetErrorString(e));
+        }
+    }
+    const uint32_t count = host ? (uint32_t)n : kNoList;
+    if (host && n)
+        GDP_HIP(h, hipMemcpyAsync(*d_in + offset, track_dma_ptr(host), n * sizeof(R), hipMemcpyHostToDevice, c->stream));
+    GDP_HIP(h, hipMemcpyAsync(d_count, &count, sizeof count, hipMemcpyHostToDevice, c->stream));
+    GDP_HIP(h, hipStreamSynchronize(c->stream));
+    return GDP_OK;
+}
+
+// Blocks per image of an orientation / descriptor launch, from the longest input list: the caller's
+// lengths (W::in_count) are known here, the producer's only on the device, so its capacity stands in.
+// A record yields at most `yield` output records, and the counter is 32-bit.
+template <class W>
+int blocks_per_image(W* w, const char* who, bool producer, size_t producer_capacity, const char* no_producer, unsigned yield,
+                     unsigned per_block, unsigned long long* per_img) {
+    const int batch = w->ctx->geom.batch;
+    unsigned long long longest = 0;
+    for (int b = 0; b < batch; ++b) {
+        const uint32_t n = w->in_count[(size_t)b];
+        if (n == kNoList && !producer)
+            return w->status(GDP_ERR_STATE, "%s: image %d has no input list and %s", who, b, no_producer);
+        longest = std::max<unsigned long long>(longest, n == kNoList ? producer_capacity : n);
+    }
+    if (w->capacity > 0xffffffffull || longest * yield >= (1ull << 32))
+        return w->status(GDP_ERR_ARG, "%s: too many records for the 32-bit counter", who);
+    *per_img = std::max<unsigned long long>(1, (longest + per_block - 1) / per_block);
+    if (*per_img * (unsigned long long)batch >= (1ull << 31)) return w->status(GDP_ERR_ARG, "%s: too many records for one launch", who);
+    return GDP_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1029,28 +1242,24 @@ static hipError_t alloc_spread(gdp_ctx* c, std::string& where) {
 int gdp_create_band(gdp_ctx** out, int H, int W, int S, int O, int batch, int row_begin, int row_end, int device) try {
     if (!out) return GDP_ERR_ARG;
     *out = nullptr;
-    auto fail = [](int code, const std::string& m) {
-        g_create_error = m;
-        return code;
-    };
     if (H <= 0 || W <= 0 || S < 0 || S > 60 || batch <= 0 || O < 0)
-        return fail(GDP_ERR_ARG, "gdp_create: need H, W, batch > 0, 0 <= S <= 60, octaves >= 0");
+        return create_fail(GDP_ERR_ARG, "gdp_create: need H, W, batch > 0, 0 <= S <= 60, octaves >= 0");
     const int Omax = octaves_for(std::min(H, W));
     if (O == 0) O = Omax;
     if (O > Omax || O > kMaxOct - 1)
-        return fail(GDP_ERR_ARG, "gdp_create: octaves " + std::to_string(O) + " > floor(log2(min(H,W)))+1 = " +
+        return create_fail(GDP_ERR_ARG, "gdp_create: octaves " + std::to_string(O) + " > floor(log2(min(H,W)))+1 = " +
                                      std::to_string(Omax));
     const int align = 1 << (std::max(O, kFused) - 1);
     if (row_begin < 0 || row_end > H || row_begin >= row_end || row_begin % align != 0 ||
         (row_end != H && row_end % align != 0))
-        return fail(GDP_ERR_ARG, "gdp_create_band: rows [" + std::to_string(row_begin) + ", " +
+        return create_fail(GDP_ERR_ARG, "gdp_create_band: rows [" + std::to_string(row_begin) + ", " +
                                      std::to_string(row_end) + ") must be multiples of " + std::to_string(align));
     // Host planning first (geometry, tap tables: pure host work, no device needed), then the
     // device probe and the allocations.  Anything that throws past this point (std::bad_alloc of
     // the tap table, ...) frees the half-built context and is turned into a status by the
     // function-try-block below: no exception crosses the C ABI.
     gdp_ctx* c = new (std::nothrow) gdp_ctx();
-    if (!c) return fail(GDP_ERR_NOMEM, "host allocation failed");
+    if (!c) return create_fail(GDP_ERR_NOMEM, "host allocation failed");
     auto drop = [&c]() {  // free the half-built context exactly once
         gdp_destroy(c);
         c = nullptr;
@@ -1202,7 +1411,7 @@ int gdp_create_band(gdp_ctx** out, int H, int W, int S, int O, int batch, int ro
     if (tap_off > (1ll << 31) || min_tiles + tail_units >= (1ll << 31) || tail_per_img * batch >= (1ll << 31) ||
         grp >= (1ll << 31)) {
         drop();
-        return fail(GDP_ERR_ARG, "image/batch too large for one context (split the batch)");
+        return create_fail(GDP_ERR_ARG, "image/batch too large for one context (split the batch)");
     }
     g.tail_groups_per_img = (unsigned)tail_per_img;
     g.tail_units = (unsigned)tail_units;
@@ -1222,7 +1431,7 @@ int gdp_create_band(gdp_ctx** out, int H, int W, int S, int O, int batch, int ro
     if (retile(c, kVariants[variant_index(c->variant)].tile_cols, kVariants[variant_index(c->variant)].tile_rows) != GDP_OK) {
         const std::string m = c->err;
         drop();
-        return fail(GDP_ERR_ARG, m);
+        return create_fail(GDP_ERR_ARG, m);
     }
     conv_sweep_geom(c);
     c->h_taps.assign((size_t)tap_off, 0.0f);
@@ -1232,20 +1441,20 @@ int gdp_create_band(gdp_ctx** out, int H, int W, int S, int O, int batch, int ro
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         drop();
-        return fail(GDP_ERR_NODEV, "no HIP device visible");
+        return create_fail(GDP_ERR_NODEV, "no HIP device visible");
     }
     hipDeviceProp_t prop;
     if (device < 0 || device >= ndev) {
         drop();
-        return fail(GDP_ERR_ARG, "device index out of range");
+        return create_fail(GDP_ERR_ARG, "device index out of range");
     }
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) {
         drop();
-        return fail(GDP_ERR_NODEV, "hipGetDeviceProperties failed");
+        return create_fail(GDP_ERR_NODEV, "hipGetDeviceProperties failed");
     }
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
         drop();
-        return fail(GDP_ERR_NODEV, std::string("libgdp is built for gfx950, device is ") + prop.gcnArchName);
+        return create_fail(GDP_ERR_NODEV, std::string("libgdp is built for gfx950, device is ") + prop.gcnArchName);
     }
     c->cus = std::max(1, prop.multiProcessorCount);
     c->blocks_max = c->cus * 8;
@@ -1253,7 +1462,7 @@ int gdp_create_band(gdp_ctx** out, int H, int W, int S, int O, int batch, int ro
     auto hip_fail = [&](hipError_t e, const char* what) {
         std::string m = std::string(what) + ": " + hipGetErrorString(e);
         drop();
-        return fail(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, m);
+        return create_fail(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, m);
     };
     hipError_t e;
     if ((e = hipSetDevice(device)) != hipSuccess) return hip_fail(e, "hipSetDevice");
@@ -1288,7 +1497,7 @@ int gdp_create_band(gdp_ctx** out, int H, int W, int S, int O, int batch, int ro
             if (retile(c, kVariants[variant_index(c->variant)].tile_cols, kVariants[variant_index(c->variant)].tile_rows) != GDP_OK) {
                 const std::string m = c->err;
                 drop();
-                return fail(GDP_ERR_ARG, m);
+                return create_fail(GDP_ERR_ARG, m);
             }
         }
     }
@@ -1309,7 +1518,7 @@ int gdp_create_band(gdp_ctx** out, int H, int W, int S, int O, int batch, int ro
     if (upload_geom(c) != GDP_OK) {
         std::string m = c->err;
         drop();
-        return fail(GDP_ERR_HIP, m);
+        return create_fail(GDP_ERR_HIP, m);
     }
     *out = c;
     return GDP_OK;
@@ -2720,49 +2929,6 @@ int gdp_checksum(gdp_ctx* c, int b, uint64_t* out) try {
 } GDP_ABI_CATCH(c)
 
 // ---- extension: scale-space extrema (keypoints) on the current pyramid (gdp_extrema.inc) --------
-static int ensure_keypoints(gdp_ctx* c) {
-    if (c->d_kp && c->d_kp_count) return GDP_OK;
-    const size_t batch = (size_t)c->geom.batch;
-    hipError_t e = hipSuccess;
-    if (!c->d_kp) e = hipMalloc(reinterpret_cast<void**>(&c->d_kp), c->kp_capacity * batch * sizeof(gdp_keypoint));
-    if (e == hipSuccess && !c->d_kp_count) {
-        e = hipMalloc(reinterpret_cast<void**>(&c->d_kp_count), batch * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemset(c->d_kp_count, 0, batch * sizeof(uint32_t));
-        // hipMemset runs on the null stream, which the context's non-blocking stream does not wait for: it must
-        // have landed before a launch on that stream counts into the buffer
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    }
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return c->status(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, "keypoint buffer (%zu records x %zu images): %s",
-                         c->kp_capacity, batch, hipGetErrorString(e));
-    }
-    return GDP_OK;
-}
-
-// gdp_refine_keypoints' outputs: [batch][kp_capacity] 32-byte records and [batch] counters
-static int ensure_refined(gdp_ctx* c) {
-    if (c->d_rf && c->d_rf_count) return GDP_OK;
-    const size_t batch = (size_t)c->geom.batch;
-    hipError_t e = hipSuccess;
-    if (c->kp_capacity > (SIZE_MAX / sizeof(gdp_keypoint_refined)) / batch) e = hipErrorOutOfMemory;
-    if (e == hipSuccess && !c->d_rf)
-        e = hipMalloc(reinterpret_cast<void**>(&c->d_rf), c->kp_capacity * batch * sizeof(gdp_keypoint_refined));
-    if (e == hipSuccess && !c->d_rf_count) {
-        e = hipMalloc(reinterpret_cast<void**>(&c->d_rf_count), batch * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemset(c->d_rf_count, 0, batch * sizeof(uint32_t));
-        // hipMemset runs on the null stream, which the context's non-blocking stream does not wait for: it must
-        // have landed before a launch on that stream counts into the buffer
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    }
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return c->status(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, "refined keypoint buffer (%zu records x %zu images): %s",
-                         c->kp_capacity, batch, hipGetErrorString(e));
-    }
-    return GDP_OK;
-}
-
 int gdp_set_keypoint_capacity(gdp_ctx* c, size_t per_image) try {
     GDP_READS_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
@@ -2794,14 +2960,11 @@ int gdp_set_keypoint_capacity(gdp_ctx* c, size_t per_image) try {
 int gdp_detect_extrema(gdp_ctx* c, float contrast_threshold, float edge_ratio, void* stream) try {
     GDP_READS_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
-    if (!(contrast_threshold >= 0.0f))
-        return c->status(GDP_ERR_ARG, "gdp_detect_extrema: contrast_threshold must be >= 0");
-    if (edge_ratio != 0.0f && !(edge_ratio >= 1.0f && std::isfinite(edge_ratio)))
-        return c->status(GDP_ERR_ARG, "gdp_detect_extrema: edge_ratio must be 0 (no edge test) or finite and >= 1");
+    const int bad = check_thresholds(c, "gdp_detect_extrema", contrast_threshold, edge_ratio);
+    if (bad != GDP_OK) return bad;
     const Geom& g = c->geom;
-    if (g.in_row0 != 0 || g.in_rows != g.H)
-        return c->status(GDP_ERR_STATE, "gdp_detect_extrema: a row band does not hold its candidates' neighbours "
-                                        "across the band edges; detect on a whole-image context");
+    const std::string band = row_band_error(g, "gdp_detect_extrema", "candidates' neighbours", "detect");
+    if (!band.empty()) return c->status(GDP_ERR_STATE, "%s", band.c_str());
     unsigned long long px = 0;
     for (int o = 0; o < g.O; ++o) px += (unsigned long long)g.oct[o].rows * g.oct[o].cols;
     if ((unsigned long long)g.S * px >= (1ull << 32))
@@ -2829,40 +2992,15 @@ int gdp_keypoint_count(gdp_ctx* c, int b, size_t* found) try {
     GDP_READS_PYRAMID(c);
     if (!c || !found || b < 0 || b >= c->geom.batch)
         return c ? c->status(GDP_ERR_ARG, "gdp_keypoint_count: bad argument") : GDP_ERR_ARG;
-    *found = 0;
-    if (!c->d_kp_count) return GDP_OK;  // no detection has run
-    GDP_HIP(c, hipSetDevice(c->device));
-    uint32_t n = 0;
-    GDP_HIP(c, hipMemcpyAsync(&n, c->d_kp_count + b, sizeof n, hipMemcpyDeviceToHost, c->stream));
-    GDP_HIP(c, hipStreamSynchronize(c->stream));
-    *found = n;
-    return GDP_OK;
+    return read_counter(c, at(c->d_kp_count, b), found);  // 0 while no detection has run
 } GDP_ABI_CATCH(c)
 
 int gdp_download_keypoints(gdp_ctx* c, int b, gdp_keypoint* host, size_t capacity, size_t* stored, size_t* found) try {
     GDP_READS_PYRAMID(c);
     if (!c || b < 0 || b >= c->geom.batch || (!host && capacity))
         return c ? c->status(GDP_ERR_ARG, "gdp_download_keypoints: bad argument") : GDP_ERR_ARG;
-    if (stored) *stored = 0;
-    size_t total = 0;
-    const int rc = gdp_keypoint_count(c, b, &total);
-    if (rc != GDP_OK) return rc;
-    if (found) *found = total;
-    const size_t n = std::min(total, std::min(c->kp_capacity, capacity));
-    if (n == 0) return GDP_OK;
-    GDP_SETTLE(c, "gdp_download_keypoints", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint)); });
-    GDP_HIP(c, hipMemcpyAsync(track_dma_ptr(host), c->d_kp + (size_t)b * c->kp_capacity, n * sizeof(gdp_keypoint),
-                              hipMemcpyDeviceToHost, c->stream));
-    GDP_HIP(c, hipStreamSynchronize(c->stream));
-    // the device order depends on the waves' timing; (octave, scale, row, col) is unique per record
-    std::sort(host, host + n, [](const gdp_keypoint& p, const gdp_keypoint& q) {
-        if (p.octave != q.octave) return p.octave < q.octave;
-        if (p.scale != q.scale) return p.scale < q.scale;
-        if (p.row != q.row) return p.row < q.row;
-        return p.col < q.col;
-    });
-    if (stored) *stored = n;
-    return GDP_OK;
+    return download_sorted(c, "gdp_download_keypoints", at(c->d_kp, (size_t)b * c->kp_capacity), at(c->d_kp_count, b),
+                           c->kp_capacity, host, capacity, stored, found);
 } GDP_ABI_CATCH(c)
 
 int gdp_device_keypoints(const gdp_ctx* c, int b, const gdp_keypoint** records, const uint32_t** count) try {
@@ -2883,14 +3021,11 @@ int gdp_device_keypoints(const gdp_ctx* c, int b, const gdp_keypoint** records, 
 int gdp_refine_keypoints(gdp_ctx* c, float contrast_threshold, float edge_ratio, void* stream) try {
     GDP_READS_PYRAMID(c);
     if (!c) return GDP_ERR_ARG;
-    if (!(contrast_threshold >= 0.0f))
-        return c->status(GDP_ERR_ARG, "gdp_refine_keypoints: contrast_threshold must be >= 0");
-    if (edge_ratio != 0.0f && !(edge_ratio >= 1.0f && std::isfinite(edge_ratio)))
-        return c->status(GDP_ERR_ARG, "gdp_refine_keypoints: edge_ratio must be 0 (no edge test) or finite and >= 1");
+    const int bad = check_thresholds(c, "gdp_refine_keypoints", contrast_threshold, edge_ratio);
+    if (bad != GDP_OK) return bad;
     const Geom& g = c->geom;
-    if (g.in_row0 != 0 || g.in_rows != g.H)
-        return c->status(GDP_ERR_STATE, "gdp_refine_keypoints: a row band does not hold its keypoints' neighbours "
-                                        "across the band edges; refine on a whole-image context");
+    const std::string band = row_band_error(g, "gdp_refine_keypoints", "keypoints' neighbours", "refine");
+    if (!band.empty()) return c->status(GDP_ERR_STATE, "%s", band.c_str());
     if (!c->d_kp || !c->d_kp_count)
         return c->status(GDP_ERR_STATE, "gdp_refine_keypoints: no keypoint list yet (run gdp_detect_extrema or "
                                         "gdp_upload_keypoints first)");
@@ -2913,51 +3048,16 @@ int gdp_refined_count(gdp_ctx* c, int b, size_t* kept) try {
     GDP_READS_PYRAMID(c);
     if (!c || !kept || b < 0 || b >= c->geom.batch)
         return c ? c->status(GDP_ERR_ARG, "gdp_refined_count: bad argument") : GDP_ERR_ARG;
-    *kept = 0;
-    if (!c->d_rf_count) return GDP_OK;  // no refinement has run
-    GDP_HIP(c, hipSetDevice(c->device));
-    uint32_t n = 0;
-    GDP_HIP(c, hipMemcpyAsync(&n, c->d_rf_count + b, sizeof n, hipMemcpyDeviceToHost, c->stream));
-    GDP_HIP(c, hipStreamSynchronize(c->stream));
-    *kept = n;
-    return GDP_OK;
+    return read_counter(c, at(c->d_rf_count, b), kept);  // 0 while no refinement has run
 } GDP_ABI_CATCH(c)
 
 int gdp_download_refined(gdp_ctx* c, int b, gdp_keypoint_refined* host, size_t capacity, size_t* stored) try {
     GDP_READS_PYRAMID(c);
     if (!c || b < 0 || b >= c->geom.batch || (!host && capacity))
         return c ? c->status(GDP_ERR_ARG, "gdp_download_refined: bad argument") : GDP_ERR_ARG;
-    if (stored) *stored = 0;
-    size_t total = 0;
-    const int rc = gdp_refined_count(c, b, &total);
-    if (rc != GDP_OK) return rc;
-    const size_t n = std::min(total, std::min(c->kp_capacity, capacity));
-    if (n == 0 || !c->d_rf) return GDP_OK;
-    GDP_SETTLE(c, "gdp_download_refined", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint_refined)); });
-    GDP_HIP(c, hipMemcpyAsync(track_dma_ptr(host), c->d_rf + (size_t)b * c->kp_capacity, n * sizeof(gdp_keypoint_refined),
-                              hipMemcpyDeviceToHost, c->stream));
-    GDP_HIP(c, hipStreamSynchronize(c->stream));
-    // the device order depends on the waves' timing, and two inputs may end at the same sample:
-    // the position first, then the bits of everything else, so equal keys are identical records
-    auto bits = [](float f) {
-        uint32_t u;
-        std::memcpy(&u, &f, sizeof u);
-        return u;
-    };
-    std::sort(host, host + n, [&](const gdp_keypoint_refined& p, const gdp_keypoint_refined& q) {
-        if (p.octave != q.octave) return p.octave < q.octave;
-        if (p.scale != q.scale) return p.scale < q.scale;
-        if (p.row != q.row) return p.row < q.row;
-        if (p.col != q.col) return p.col < q.col;
-        if (bits(p.dscale) != bits(q.dscale)) return bits(p.dscale) < bits(q.dscale);
-        if (bits(p.drow) != bits(q.drow)) return bits(p.drow) < bits(q.drow);
-        if (bits(p.dcol) != bits(q.dcol)) return bits(p.dcol) < bits(q.dcol);
-        if (bits(p.interp) != bits(q.interp)) return bits(p.interp) < bits(q.interp);
-        if (bits(p.value) != bits(q.value)) return bits(p.value) < bits(q.value);
-        return (uint8_t)p.kind < (uint8_t)q.kind;
-    });
-    if (stored) *stored = n;
-    return GDP_OK;
+    // no `found`; nothing is stored while no refinement has run
+    return download_sorted(c, "gdp_download_refined", at(c->d_rf, (size_t)b * c->kp_capacity), at(c->d_rf_count, b),
+                           c->kp_capacity, host, capacity, stored, nullptr);
 } GDP_ABI_CATCH(c)
 
 int gdp_device_refined(const gdp_ctx* c, int b, const gdp_keypoint_refined** records, const uint32_t** count) try {
@@ -2982,10 +3082,7 @@ int gdp_upload_keypoints(gdp_ctx* c, int b, const gdp_keypoint* host, size_t n) 
     if (n) GDP_SETTLE(c, "gdp_upload_keypoints", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint)); });
     for (size_t i = 0; i < n; ++i) {
         const gdp_keypoint& k = host[i];
-        const bool ok = (int)k.octave < g.O && k.scale >= 1 && (int)k.scale <= g.S && k.row >= 1 &&
-                        k.row <= g.oct[std::min<int>(k.octave, g.O - 1)].rows - 2 && k.col >= 1 &&
-                        k.col <= g.oct[std::min<int>(k.octave, g.O - 1)].cols - 2 && (k.kind == 1 || k.kind == -1);
-        if (!ok)
+        if (!names_sample(g, k) || (k.kind != 1 && k.kind != -1))
             return c->status(GDP_ERR_ARG, "gdp_upload_keypoints: record %zu (octave %d, scale %d, row %d, col %d, kind %d) is no "
                                           "candidate of this context", i, (int)k.octave, (int)k.scale, (int)k.row, (int)k.col, (int)k.kind);
     }
@@ -3003,20 +3100,6 @@ int gdp_upload_keypoints(gdp_ctx* c, int b, const gdp_keypoint* host, size_t n) 
 // ---- extension: orientation assignment of the refined list (gdp_orient.inc) ----------------------
 // No export below takes a mutable context: the state is the gdp_orient object's, the context is
 // read (k_orient takes the pyramid and the refined list const), so a build that follows is a kept one.
-static int orient_exception(gdp_orient* w, int code, const char* what) noexcept {
-    try {
-        if (w)
-            w->err = what;
-        else
-            g_create_error = what;
-    } catch (...) {
-    }
-    return code;
-}
-#define GDP_ORIENT_CATCH(w)                                                                                   \
-    catch (const std::bad_alloc&) { return orient_exception((w), GDP_ERR_NOMEM, "host allocation failed (std::bad_alloc)"); } \
-    catch (const std::exception& e_) { return orient_exception((w), GDP_ERR_INTERNAL, e_.what()); }         \
-    catch (...) { return orient_exception((w), GDP_ERR_INTERNAL, "unknown C++ exception"); }
 
 // w_s[d2] = expf(-((float)d2 * k_s)), k_s = (float)((s+1)^2) / 18.0f, for d2 = 0 .. 2 R_s^2; returns R_s
 static int orient_weights_of(int s, float* out) {
@@ -3046,47 +3129,25 @@ void gdp_orient_destroy(gdp_orient* w) {
 
 int gdp_orient_create(gdp_orient** out, const gdp_ctx* c, size_t capacity_per_image) try {
     if (!out || !c) return GDP_ERR_ARG;
-    auto fail = [&](int code, const std::string& m) {
-        g_create_error = m;
-        return code;
-    };
     const Geom& g = c->geom;
-    if (g.in_row0 != 0 || g.in_rows != g.H)
-        return fail(GDP_ERR_STATE, "gdp_orient_create: a row band does not hold its keypoints' windows across the band "
-                                   "edges; orient on a whole-image context");
+    const std::string band = row_band_error(g, "gdp_orient_create", "keypoints' windows", "orient");
+    if (!band.empty()) return create_fail(GDP_ERR_STATE, band);
     const size_t batch = (size_t)g.batch;
     if (capacity_per_image == 0) {
-        if (c->kp_capacity > SIZE_MAX / 2) return fail(GDP_ERR_ARG, "gdp_orient_create: capacity does not fit the address space");
+        if (c->kp_capacity > SIZE_MAX / 2) return create_fail(GDP_ERR_ARG, "gdp_orient_create: capacity does not fit the address space");
         capacity_per_image = 2 * c->kp_capacity;
     }
     if (capacity_per_image > (SIZE_MAX / sizeof(gdp_keypoint_oriented)) / batch)
-        return fail(GDP_ERR_ARG, "gdp_orient_create: capacity does not fit the address space");
+        return create_fail(GDP_ERR_ARG, "gdp_orient_create: capacity does not fit the address space");
     hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return create_fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
     gdp_orient* w = new gdp_orient;
     w->ctx = c;
     w->capacity = capacity_per_image;
     w->in_count.assign(batch, kOrNoList);
     std::vector<float> table((size_t)std::max(g.S, 1) * kOrWeights, 0.0f);
     for (int s = 1; s <= g.S; ++s) (void)orient_weights_of(s, table.data() + (size_t)(s - 1) * kOrWeights);
-    e = hipMalloc(reinterpret_cast<void**>(&w->d_weights), table.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(w->d_weights, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_out), w->capacity * batch * sizeof(gdp_keypoint_oriented));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_count), batch * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(w->d_count, 0, batch * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_in_count), batch * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(w->d_in_count, 0xff, batch * sizeof(uint32_t));  // kOrNoList
-    // hipMemset runs on the null stream, which the context's non-blocking stream does not wait for
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        const std::string m = std::string("gdp_orient_create (") + std::to_string(w->capacity) + " records x " +
-                              std::to_string(batch) + " images): " + hipGetErrorString(e);
-        gdp_orient_destroy(w);
-        return fail(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, m);
-    }
-    *out = w;
-    return GDP_OK;
+    return finish_create(out, w, gdp_orient_destroy, "gdp_orient_create", batch, upload_table(&w->d_weights, table));
 } GDP_ABI_CATCH(nullptr)
 
 const char* gdp_orient_last_error(const gdp_orient* w) { return w ? w->err.c_str() : g_create_error.c_str(); }
@@ -3098,54 +3159,26 @@ int gdp_orient_set_input(gdp_orient* w, int b, const gdp_keypoint_refined* host,
     if (b < 0 || b >= g.batch) return w->status(GDP_ERR_ARG, "gdp_orient_set_input: bad argument");
     if (host && n > w->capacity)
         return w->status(GDP_ERR_ARG, "gdp_orient_set_input: %zu records exceed the capacity %zu", n, w->capacity);
-    GDP_HIP(w, hipSetDevice(c->device));
-    if (host && n) GDP_SETTLE(w, "gdp_orient_set_input", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint_refined)); });
-    for (size_t i = 0; host && i < n; ++i) {
-        const gdp_keypoint_refined& k = host[i];
-        const bool ok = (int)k.octave < g.O && k.scale >= 1 && (int)k.scale <= g.S && k.row >= 1 &&
-                        k.row <= g.oct[std::min<int>(k.octave, g.O - 1)].rows - 2 && k.col >= 1 &&
-                        k.col <= g.oct[std::min<int>(k.octave, g.O - 1)].cols - 2 && (k.kind == 1 || k.kind == -1);
-        if (!ok)
-            return w->status(GDP_ERR_ARG, "gdp_orient_set_input: record %zu (octave %d, scale %d, row %d, col %d, kind %d) names "
-                                          "no sample of this context", i, (int)k.octave, (int)k.scale, (int)k.row, (int)k.col, (int)k.kind);
-    }
-    if (host && !w->d_in) {
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&w->d_in), w->capacity * (size_t)g.batch * sizeof(gdp_keypoint_refined));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            w->d_in = nullptr;
-            return w->status(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, "gdp_orient_set_input: input buffer: %s", hipGetErrorString(e));
-        }
-    }
-    const uint32_t count = host ? (uint32_t)n : kOrNoList;
-    if (host && n)
-        GDP_HIP(w, hipMemcpyAsync(w->d_in + (size_t)b * w->capacity, track_dma_ptr(host), n * sizeof(gdp_keypoint_refined),
-                                  hipMemcpyHostToDevice, c->stream));
-    GDP_HIP(w, hipMemcpyAsync(w->d_in_count + b, &count, sizeof count, hipMemcpyHostToDevice, c->stream));
-    GDP_HIP(w, hipStreamSynchronize(c->stream));
-    w->in_count[(size_t)b] = count;
-    return GDP_OK;
-} GDP_ORIENT_CATCH(w)
+    const int rc = replace_input(w, "gdp_orient_set_input", &w->d_in, w->capacity * (size_t)g.batch, (size_t)b * w->capacity,
+                                 w->d_in_count + b, host, n, [&](size_t i, const gdp_keypoint_refined& k) {
+        if (names_sample(g, k) && (k.kind == 1 || k.kind == -1)) return (int)GDP_OK;
+        return w->status(GDP_ERR_ARG, "gdp_orient_set_input: record %zu (octave %d, scale %d, row %d, col %d, kind %d) names "
+                                      "no sample of this context", i, (int)k.octave, (int)k.scale, (int)k.row, (int)k.col, (int)k.kind);
+    });
+    if (rc == GDP_OK) w->in_count[(size_t)b] = host ? (uint32_t)n : kNoList;
+    return rc;
+} GDP_ABI_CATCH(w)
 
 int gdp_orient_keypoints(gdp_orient* w, void* stream) try {
     if (!w) return GDP_ERR_ARG;
     const gdp_ctx* c = w->ctx;
     const Geom& g = c->geom;
-    // inputs of the longest list: the caller's lengths are known here, the context's only on the device
-    unsigned long long longest = 0;
-    for (int b = 0; b < g.batch; ++b) {
-        const uint32_t n = w->in_count[(size_t)b];
-        if (n == kOrNoList && (!c->d_rf || !c->d_rf_count))
-            return w->status(GDP_ERR_STATE, "gdp_orient_keypoints: image %d has no input list and the context no refined "
-                                            "buffer yet (run gdp_refine_keypoints or gdp_orient_set_input first)", b);
-        longest = std::max<unsigned long long>(longest, n == kOrNoList ? c->kp_capacity : n);
-    }
-    // a record yields at most 18 peaks (strict local maxima of 36 circular bins); the counter is 32-bit
-    if (w->capacity > 0xffffffffull || longest * 18 >= (1ull << 32))
-        return w->status(GDP_ERR_ARG, "gdp_orient_keypoints: too many records for the 32-bit counter");
-    const unsigned long long per_img = std::max<unsigned long long>(1, (longest + kOrPerBlock - 1) / kOrPerBlock);
-    if (per_img * (unsigned long long)g.batch >= (1ull << 31))
-        return w->status(GDP_ERR_ARG, "gdp_orient_keypoints: too many records for one launch");
+    unsigned long long per_img = 0;
+    // a record yields at most 18 peaks (strict local maxima of 36 circular bins)
+    const int rc = blocks_per_image(w, "gdp_orient_keypoints", c->d_rf && c->d_rf_count, c->kp_capacity,
+                                    "the context no refined buffer yet (run gdp_refine_keypoints or gdp_orient_set_input first)",
+                                    18, kOrPerBlock, &per_img);
+    if (rc != GDP_OK) return rc;
     GDP_HIP(w, hipSetDevice(c->device));
     hipStream_t st = c->pick(stream);
     GDP_HIP(w, hipMemsetAsync(w->d_count, 0, (size_t)g.batch * sizeof(uint32_t), st));
@@ -3155,51 +3188,22 @@ int gdp_orient_keypoints(gdp_orient* w, void* stream) try {
                        w->d_count, (unsigned long long)w->capacity, (unsigned)per_img);
     GDP_HIP(w, hipGetLastError());
     return GDP_OK;
-} GDP_ORIENT_CATCH(w)
+} GDP_ABI_CATCH(w)
 
 int gdp_oriented_count(gdp_orient* w, int b, size_t* found) try {
     if (!w || !found) return w ? w->status(GDP_ERR_ARG, "gdp_oriented_count: bad argument") : GDP_ERR_ARG;
     const gdp_ctx* c = w->ctx;
     if (b < 0 || b >= c->geom.batch) return w->status(GDP_ERR_ARG, "gdp_oriented_count: bad argument");
-    GDP_HIP(w, hipSetDevice(c->device));
-    uint32_t n = 0;
-    GDP_HIP(w, hipMemcpyAsync(&n, w->d_count + b, sizeof n, hipMemcpyDeviceToHost, c->stream));
-    GDP_HIP(w, hipStreamSynchronize(c->stream));
-    *found = n;
-    return GDP_OK;
-} GDP_ORIENT_CATCH(w)
+    return read_counter(w, w->d_count + b, found);
+} GDP_ABI_CATCH(w)
 
 int gdp_download_oriented(gdp_orient* w, int b, gdp_keypoint_oriented* host, size_t capacity, size_t* stored, size_t* found) try {
     if (!w) return GDP_ERR_ARG;
     const gdp_ctx* c = w->ctx;
     if (b < 0 || b >= c->geom.batch || (!host && capacity)) return w->status(GDP_ERR_ARG, "gdp_download_oriented: bad argument");
-    if (stored) *stored = 0;
-    size_t total = 0;
-    const int rc = gdp_oriented_count(w, b, &total);
-    if (rc != GDP_OK) return rc;
-    if (found) *found = total;
-    const size_t n = std::min(total, std::min(w->capacity, capacity));
-    if (n == 0) return GDP_OK;
-    GDP_SETTLE(w, "gdp_download_oriented", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint_oriented)); });
-    GDP_HIP(w, hipMemcpyAsync(track_dma_ptr(host), w->d_out + (size_t)b * w->capacity, n * sizeof(gdp_keypoint_oriented),
-                              hipMemcpyDeviceToHost, c->stream));
-    GDP_HIP(w, hipStreamSynchronize(c->stream));
-    // the device order depends on the waves' timing, and two inputs may name the same sample: the
-    // position and the bin first, then the record's words, so equal keys are identical records
-    std::sort(host, host + n, [](const gdp_keypoint_oriented& p, const gdp_keypoint_oriented& q) {
-        if (p.octave != q.octave) return p.octave < q.octave;
-        if (p.scale != q.scale) return p.scale < q.scale;
-        if (p.row != q.row) return p.row < q.row;
-        if (p.col != q.col) return p.col < q.col;
-        if (p.bin != q.bin) return p.bin < q.bin;
-        uint32_t a[12], z[12];
-        std::memcpy(a, &p, sizeof a);
-        std::memcpy(z, &q, sizeof z);
-        return std::lexicographical_compare(a, a + 12, z, z + 12);
-    });
-    if (stored) *stored = n;
-    return GDP_OK;
-} GDP_ORIENT_CATCH(w)
+    return download_sorted(w, "gdp_download_oriented", w->d_out + (size_t)b * w->capacity, w->d_count + b, w->capacity, host, capacity,
+                           stored, found);
+} GDP_ABI_CATCH(w)
 
 int gdp_device_oriented(const gdp_orient* w, int b, const gdp_keypoint_oriented** records, const uint32_t** count) try {
     if (!w || b < 0 || b >= w->ctx->geom.batch) return GDP_ERR_ARG;
@@ -3211,20 +3215,6 @@ int gdp_device_oriented(const gdp_orient* w, int b, const gdp_keypoint_oriented*
 // ---- extension: SIFT descriptors of the oriented list (gdp_describe.inc) --------------------------
 // No export below takes a mutable context or a mutable orientation object: the state is the
 // gdp_describe object's, everything else is read (k_describe takes the pyramid and the lists const).
-static int describe_exception(gdp_describe* w, int code, const char* what) noexcept {
-    try {
-        if (w)
-            w->err = what;
-        else
-            g_create_error = what;
-    } catch (...) {
-    }
-    return code;
-}
-#define GDP_DESCRIBE_CATCH(w)                                                                                 \
-    catch (const std::bad_alloc&) { return describe_exception((w), GDP_ERR_NOMEM, "host allocation failed (std::bad_alloc)"); } \
-    catch (const std::exception& e_) { return describe_exception((w), GDP_ERR_INTERNAL, e_.what()); }       \
-    catch (...) { return describe_exception((w), GDP_ERR_INTERNAL, "unknown C++ exception"); }
 
 // W_s[d2] = expf(-((float)d2 * k_s)), k_s = (float)((s+1)^2) / 288.0f, for d2 = 0 .. 2 R_s^2; returns R_s
 static int describe_weights_of(int s, float* out) {
@@ -3276,21 +3266,16 @@ void gdp_describe_destroy(gdp_describe* w) {
 
 int gdp_describe_create(gdp_describe** out, const gdp_ctx* c, const gdp_orient* src, size_t capacity_per_image) try {
     if (!out || !c) return GDP_ERR_ARG;
-    auto fail = [&](int code, const std::string& m) {
-        g_create_error = m;
-        return code;
-    };
-    if (src && src->ctx != c) return fail(GDP_ERR_ARG, "gdp_describe_create: the orientation object belongs to another context");
+    if (src && src->ctx != c) return create_fail(GDP_ERR_ARG, "gdp_describe_create: the orientation object belongs to another context");
     const Geom& g = c->geom;
-    if (g.in_row0 != 0 || g.in_rows != g.H)
-        return fail(GDP_ERR_STATE, "gdp_describe_create: a row band does not hold its keypoints' windows across the band "
-                                   "edges; describe on a whole-image context");
+    const std::string band = row_band_error(g, "gdp_describe_create", "keypoints' windows", "describe");
+    if (!band.empty()) return create_fail(GDP_ERR_STATE, band);
     const size_t batch = (size_t)g.batch;
     if (capacity_per_image == 0) capacity_per_image = src ? src->capacity : c->kp_capacity;
     if (capacity_per_image == 0 || capacity_per_image > (SIZE_MAX / sizeof(gdp_keypoint_described)) / batch)
-        return fail(GDP_ERR_ARG, "gdp_describe_create: capacity does not fit the address space");
+        return create_fail(GDP_ERR_ARG, "gdp_describe_create: capacity does not fit the address space");
     hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return create_fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
     gdp_describe* w = new gdp_describe;
     w->ctx = c;
     w->src = src;
@@ -3300,26 +3285,9 @@ int gdp_describe_create(gdp_describe** out, const gdp_ctx* c, const gdp_orient* 
     for (int s = 1; s <= g.S; ++s) (void)describe_weights_of(s, table.data() + (size_t)(s - 1) * kDeWeights);
     std::vector<float> rot(2 * (size_t)kDeAngles);
     describe_rotation(rot.data(), rot.data() + kDeAngles);
-    e = hipMalloc(reinterpret_cast<void**>(&w->d_weights), table.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(w->d_weights, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_rot), rot.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(w->d_rot, rot.data(), rot.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_out), w->capacity * batch * sizeof(gdp_keypoint_described));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_count), batch * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(w->d_count, 0, batch * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_in_count), batch * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(w->d_in_count, 0xff, batch * sizeof(uint32_t));  // kDeNoList
-    // hipMemset runs on the null stream, which the context's non-blocking stream does not wait for
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        const std::string m = std::string("gdp_describe_create (") + std::to_string(w->capacity) + " records x " +
-                              std::to_string(batch) + " images): " + hipGetErrorString(e);
-        gdp_describe_destroy(w);
-        return fail(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, m);
-    }
-    *out = w;
-    return GDP_OK;
+    e = upload_table(&w->d_weights, table);
+    if (e == hipSuccess) e = upload_table(&w->d_rot, rot);
+    return finish_create(out, w, gdp_describe_destroy, "gdp_describe_create", batch, e);
 } GDP_ABI_CATCH(nullptr)
 
 const char* gdp_describe_last_error(const gdp_describe* w) { return w ? w->err.c_str() : g_create_error.c_str(); }
@@ -3331,57 +3299,28 @@ int gdp_describe_set_input(gdp_describe* w, int b, const gdp_keypoint_oriented* 
     if (b < 0 || b >= g.batch) return w->status(GDP_ERR_ARG, "gdp_describe_set_input: bad argument");
     if (host && n > w->capacity)
         return w->status(GDP_ERR_ARG, "gdp_describe_set_input: %zu records exceed the capacity %zu", n, w->capacity);
-    GDP_HIP(w, hipSetDevice(c->device));
-    if (host && n) GDP_SETTLE(w, "gdp_describe_set_input", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint_oriented)); });
-    for (size_t i = 0; host && i < n; ++i) {
-        // exactly what k_describe checks before it forms an address
-        const gdp_keypoint_oriented& k = host[i];
-        const bool ok = (int)k.octave < g.O && k.scale >= 1 && (int)k.scale <= g.S && k.row >= 1 &&
-                        k.row <= g.oct[std::min<int>(k.octave, g.O - 1)].rows - 2 && k.col >= 1 &&
-                        k.col <= g.oct[std::min<int>(k.octave, g.O - 1)].cols - 2 && 0.0f <= k.angle && k.angle < 360.0f;
-        if (!ok)
-            return w->status(GDP_ERR_ARG, "gdp_describe_set_input: record %zu (octave %d, scale %d, row %d, col %d, angle %g) names "
-                                          "no sample of this context or no angle in [0, 360)", i, (int)k.octave, (int)k.scale,
-                             (int)k.row, (int)k.col, (double)k.angle);
-    }
-    if (host && !w->d_in) {
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&w->d_in), w->capacity * (size_t)g.batch * sizeof(gdp_keypoint_oriented));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            w->d_in = nullptr;
-            return w->status(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, "gdp_describe_set_input: input buffer: %s", hipGetErrorString(e));
-        }
-    }
-    const uint32_t count = host ? (uint32_t)n : kDeNoList;
-    if (host && n)
-        GDP_HIP(w, hipMemcpyAsync(w->d_in + (size_t)b * w->capacity, track_dma_ptr(host), n * sizeof(gdp_keypoint_oriented),
-                                  hipMemcpyHostToDevice, c->stream));
-    GDP_HIP(w, hipMemcpyAsync(w->d_in_count + b, &count, sizeof count, hipMemcpyHostToDevice, c->stream));
-    GDP_HIP(w, hipStreamSynchronize(c->stream));
-    w->in_count[(size_t)b] = count;
-    return GDP_OK;
-} GDP_DESCRIBE_CATCH(w)
+    const int rc = replace_input(w, "gdp_describe_set_input", &w->d_in, w->capacity * (size_t)g.batch, (size_t)b * w->capacity,
+                                 w->d_in_count + b, host, n, [&](size_t i, const gdp_keypoint_oriented& k) {
+        if (names_sample(g, k) && 0.0f <= k.angle && k.angle < 360.0f) return (int)GDP_OK;
+        return w->status(GDP_ERR_ARG, "gdp_describe_set_input: record %zu (octave %d, scale %d, row %d, col %d, angle %g) names "
+                                      "no sample of this context or no angle in [0, 360)", i, (int)k.octave, (int)k.scale,
+                         (int)k.row, (int)k.col, (double)k.angle);
+    });
+    if (rc == GDP_OK) w->in_count[(size_t)b] = host ? (uint32_t)n : kNoList;
+    return rc;
+} GDP_ABI_CATCH(w)
 
 int gdp_describe_keypoints(gdp_describe* w, void* stream) try {
     if (!w) return GDP_ERR_ARG;
     const gdp_ctx* c = w->ctx;
     const gdp_orient* src = w->src;
     const Geom& g = c->geom;
-    // inputs of the longest list: the caller's lengths are known here, the orientation's only on the device
-    unsigned long long longest = 0;
-    for (int b = 0; b < g.batch; ++b) {
-        const uint32_t n = w->in_count[(size_t)b];
-        if (n == kDeNoList && !src)
-            return w->status(GDP_ERR_STATE, "gdp_describe_keypoints: image %d has no input list and the object no orientation "
-                                            "object to read (gdp_describe_set_input, or create it with one)", b);
-        longest = std::max<unsigned long long>(longest, n == kDeNoList ? src->capacity : n);
-    }
-    // one record per input at most; the counter is 32-bit
-    if (w->capacity > 0xffffffffull || longest >= (1ull << 32))
-        return w->status(GDP_ERR_ARG, "gdp_describe_keypoints: too many records for the 32-bit counter");
-    const unsigned long long per_img = std::max<unsigned long long>(1, (longest + kDePerBlock - 1) / kDePerBlock);
-    if (per_img * (unsigned long long)g.batch >= (1ull << 31))
-        return w->status(GDP_ERR_ARG, "gdp_describe_keypoints: too many records for one launch");
+    unsigned long long per_img = 0;
+    // one record per input at most
+    const int rc = blocks_per_image(w, "gdp_describe_keypoints", src != nullptr, src ? src->capacity : 0,
+                                    "the object no orientation object to read (gdp_describe_set_input, or create it with one)",
+                                    1, kDePerBlock, &per_img);
+    if (rc != GDP_OK) return rc;
     GDP_HIP(w, hipSetDevice(c->device));
     hipStream_t st = c->pick(stream);
     GDP_HIP(w, hipMemsetAsync(w->d_count, 0, (size_t)g.batch * sizeof(uint32_t), st));
@@ -3392,52 +3331,22 @@ int gdp_describe_keypoints(gdp_describe* w, void* stream) try {
                        (unsigned long long)w->capacity, (unsigned)per_img);
     GDP_HIP(w, hipGetLastError());
     return GDP_OK;
-} GDP_DESCRIBE_CATCH(w)
+} GDP_ABI_CATCH(w)
 
 int gdp_described_count(gdp_describe* w, int b, size_t* found) try {
     if (!w || !found) return w ? w->status(GDP_ERR_ARG, "gdp_described_count: bad argument") : GDP_ERR_ARG;
     const gdp_ctx* c = w->ctx;
     if (b < 0 || b >= c->geom.batch) return w->status(GDP_ERR_ARG, "gdp_described_count: bad argument");
-    GDP_HIP(w, hipSetDevice(c->device));
-    uint32_t n = 0;
-    GDP_HIP(w, hipMemcpyAsync(&n, w->d_count + b, sizeof n, hipMemcpyDeviceToHost, c->stream));
-    GDP_HIP(w, hipStreamSynchronize(c->stream));
-    *found = n;
-    return GDP_OK;
-} GDP_DESCRIBE_CATCH(w)
+    return read_counter(w, w->d_count + b, found);
+} GDP_ABI_CATCH(w)
 
 int gdp_download_described(gdp_describe* w, int b, gdp_keypoint_described* host, size_t capacity, size_t* stored, size_t* found) try {
     if (!w) return GDP_ERR_ARG;
     const gdp_ctx* c = w->ctx;
     if (b < 0 || b >= c->geom.batch || (!host && capacity)) return w->status(GDP_ERR_ARG, "gdp_download_described: bad argument");
-    if (stored) *stored = 0;
-    size_t total = 0;
-    const int rc = gdp_described_count(w, b, &total);
-    if (rc != GDP_OK) return rc;
-    if (found) *found = total;
-    const size_t n = std::min(total, std::min(w->capacity, capacity));
-    if (n == 0) return GDP_OK;
-    GDP_SETTLE(w, "gdp_download_described", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint_described)); });
-    GDP_HIP(w, hipMemcpyAsync(track_dma_ptr(host), w->d_out + (size_t)b * w->capacity, n * sizeof(gdp_keypoint_described),
-                              hipMemcpyDeviceToHost, c->stream));
-    GDP_HIP(w, hipStreamSynchronize(c->stream));
-    // the device order depends on the waves' timing, and two inputs may name the same sample: the
-    // position and the bin first, then the record's words, so equal keys are identical records
-    constexpr size_t kWords = sizeof(gdp_keypoint_described) / sizeof(uint32_t);
-    std::sort(host, host + n, [](const gdp_keypoint_described& p, const gdp_keypoint_described& q) {
-        if (p.octave != q.octave) return p.octave < q.octave;
-        if (p.scale != q.scale) return p.scale < q.scale;
-        if (p.row != q.row) return p.row < q.row;
-        if (p.col != q.col) return p.col < q.col;
-        if (p.bin != q.bin) return p.bin < q.bin;
-        uint32_t a[kWords], z[kWords];
-        std::memcpy(a, &p, sizeof a);
-        std::memcpy(z, &q, sizeof z);
-        return std::lexicographical_compare(a, a + kWords, z, z + kWords);
-    });
-    if (stored) *stored = n;
-    return GDP_OK;
-} GDP_DESCRIBE_CATCH(w)
+    return download_sorted(w, "gdp_download_described", w->d_out + (size_t)b * w->capacity, w->d_count + b, w->capacity, host, capacity,
+                           stored, found);
+} GDP_ABI_CATCH(w)
 
 int gdp_device_described(const gdp_describe* w, int b, const gdp_keypoint_described** records, const uint32_t** count) try {
     if (!w || b < 0 || b >= w->ctx->geom.batch) return GDP_ERR_ARG;
@@ -3449,20 +3358,6 @@ int gdp_device_described(const gdp_describe* w, int b, const gdp_keypoint_descri
 // ---- extension: descriptor matching (gdp_match.inc) ------------------------------------------------
 // No export below takes a mutable context, orientation object or describe object: the state is the
 // gdp_match object's, the two describe objects are read (k_match_* take their lists const).
-static int match_exception(gdp_match* m, int code, const char* what) noexcept {
-    try {
-        if (m)
-            m->err = what;
-        else
-            g_create_error = what;
-    } catch (...) {
-    }
-    return code;
-}
-#define GDP_MATCH_CATCH(m)                                                                                    \
-    catch (const std::bad_alloc&) { return match_exception((m), GDP_ERR_NOMEM, "host allocation failed (std::bad_alloc)"); } \
-    catch (const std::exception& e_) { return match_exception((m), GDP_ERR_INTERNAL, e_.what()); }          \
-    catch (...) { return match_exception((m), GDP_ERR_INTERNAL, "unknown C++ exception"); }
 
 // chunks of the OTHER list for a pass whose lane axis holds `lanes_pad / kMaTile` tiles: enough for
 // kMaTargetWaves waves in the capacity grid, never shorter than kMaChunkUnit records
@@ -3492,19 +3387,15 @@ void gdp_match_destroy(gdp_match* m) {
 int gdp_match_create(gdp_match** out, const gdp_describe* query, const gdp_describe* train, size_t query_capacity,
                      size_t train_capacity) try {
     if (!out || !query || !train) return GDP_ERR_ARG;
-    auto fail = [&](int code, const std::string& msg) {
-        g_create_error = msg;
-        return code;
-    };
     if (query->ctx->device != train->ctx->device)
-        return fail(GDP_ERR_ARG, "gdp_match_create: the two describe objects are on different devices");
+        return create_fail(GDP_ERR_ARG, "gdp_match_create: the two describe objects are on different devices");
     if (query_capacity == 0) query_capacity = query->capacity;
     if (train_capacity == 0) train_capacity = train->capacity;
     // indices and the counter are 32-bit, 0xffffffff is "none", and the grids are sized from these
     if (query_capacity > (1ull << 30) || train_capacity > (1ull << 30))
-        return fail(GDP_ERR_ARG, "gdp_match_create: a capacity above 2^30 records");
+        return create_fail(GDP_ERR_ARG, "gdp_match_create: a capacity above 2^30 records");
     hipError_t e = hipSetDevice(query->ctx->device);
-    if (e != hipSuccess) return fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return create_fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
     gdp_match* m = new gdp_match;
     m->side[0] = query;
     m->side[1] = train;
@@ -3514,25 +3405,16 @@ int gdp_match_create(gdp_match** out, const gdp_describe* query, const gdp_descr
     for (int s = 0; s < 2; ++s) m->pad[s] = (size_t)round_up((long long)m->cap[s], kMaTile);
     m->chunks[0] = match_chunks(m->pad[0], m->cap[1]);
     m->chunks[1] = match_chunks(m->pad[1], m->cap[0]);
-    e = hipMalloc(reinterpret_cast<void**>(&m->d_out), m->cap[0] * sizeof(gdp_match_record));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_count), sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(m->d_count, 0, sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_in_count), 2 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(m->d_in_count, 0xff, 2 * sizeof(uint32_t));  // kMaNoList
+    e = alloc_list(&m->d_out, m->cap[0], &m->d_count, 1);
+    if (e == hipSuccess) e = alloc_counters(&m->d_in_count, 2, 0xff);  // kNoList
     for (int s = 0; s < 2 && e == hipSuccess; ++s) {
         e = hipMalloc(reinterpret_cast<void**>(&m->d_norm[s]), m->pad[s] * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_kb[s]), m->pad[s] * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_part[s]), m->chunks[s] * m->pad[s] * sizeof(uint4));
     }
-    // hipMemset runs on the null stream, which the context's non-blocking stream does not wait for
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        const std::string msg = std::string("gdp_match_create (") + std::to_string(m->cap[0]) + " x " + std::to_string(m->cap[1]) +
-                                " records): " + hipGetErrorString(e);
-        gdp_match_destroy(m);
-        return fail(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, msg);
-    }
+    if (e != hipSuccess)
+        return create_failed(m, gdp_match_destroy, "gdp_match_create (" + std::to_string(m->cap[0]) + " x " + std::to_string(m->cap[1]) +
+                                                       " records): ", e);
     *out = m;
     return GDP_OK;
 } GDP_ABI_CATCH(nullptr)
@@ -3555,26 +3437,11 @@ int gdp_match_set_input(gdp_match* m, int side, const gdp_keypoint_described* ho
     if (side != 0 && side != 1) return m->status(GDP_ERR_ARG, "gdp_match_set_input: side is 0 (query) or 1 (train)");
     if (host && n > m->cap[side])
         return m->status(GDP_ERR_ARG, "gdp_match_set_input: %zu records exceed the capacity %zu", n, m->cap[side]);
-    GDP_HIP(m, hipSetDevice(m->device));
-    if (host && n) GDP_SETTLE(m, "gdp_match_set_input", [&](auto&& f) { f(host, n * sizeof(gdp_keypoint_described)); });
-    if (host && !m->d_in[side]) {
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->d_in[side]), m->cap[side] * sizeof(gdp_keypoint_described));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            m->d_in[side] = nullptr;
-            return m->status(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, "gdp_match_set_input: input buffer: %s", hipGetErrorString(e));
-        }
-    }
     // nothing is validated per record: the kernels read octave, row, col, drow, dcol and desc as data
     // and form no address from them
-    hipStream_t st = m->side[0]->ctx->stream;
-    const uint32_t count = host ? (uint32_t)n : kMaNoList;
-    if (host && n)
-        GDP_HIP(m, hipMemcpyAsync(m->d_in[side], track_dma_ptr(host), n * sizeof(gdp_keypoint_described), hipMemcpyHostToDevice, st));
-    GDP_HIP(m, hipMemcpyAsync(m->d_in_count + side, &count, sizeof count, hipMemcpyHostToDevice, st));
-    GDP_HIP(m, hipStreamSynchronize(st));
-    return GDP_OK;
-} GDP_MATCH_CATCH(m)
+    return replace_input(m, "gdp_match_set_input", &m->d_in[side], m->cap[side], 0, m->d_in_count + side, host, n,
+                         [](size_t, const gdp_keypoint_described&) { return (int)GDP_OK; });
+} GDP_ABI_CATCH(m)
 
 int gdp_match_descriptors(gdp_match* m, int query_image, int train_image, float ratio, uint32_t max_distance, int mutual,
                           void* stream) try {
@@ -3611,38 +3478,18 @@ int gdp_match_descriptors(gdp_match* m, int query_image, int train_image, float 
                        max_distance, mutual ? 1 : 0, reinterpret_cast<uint4*>(m->d_out), m->d_count);
     GDP_HIP(m, hipGetLastError());
     return GDP_OK;
-} GDP_MATCH_CATCH(m)
+} GDP_ABI_CATCH(m)
 
 int gdp_match_count(gdp_match* m, size_t* found) try {
     if (!m || !found) return m ? m->status(GDP_ERR_ARG, "gdp_match_count: bad argument") : GDP_ERR_ARG;
-    GDP_HIP(m, hipSetDevice(m->device));
-    hipStream_t st = m->side[0]->ctx->stream;
-    uint32_t n = 0;
-    GDP_HIP(m, hipMemcpyAsync(&n, m->d_count, sizeof n, hipMemcpyDeviceToHost, st));
-    GDP_HIP(m, hipStreamSynchronize(st));
-    *found = n;
-    return GDP_OK;
-} GDP_MATCH_CATCH(m)
+    return read_counter(m, m->d_count, found);
+} GDP_ABI_CATCH(m)
 
 int gdp_download_matches(gdp_match* m, gdp_match_record* host, size_t capacity, size_t* stored, size_t* found) try {
     if (!m) return GDP_ERR_ARG;
     if (!host && capacity) return m->status(GDP_ERR_ARG, "gdp_download_matches: bad argument");
-    if (stored) *stored = 0;
-    size_t total = 0;
-    const int rc = gdp_match_count(m, &total);
-    if (rc != GDP_OK) return rc;
-    if (found) *found = total;
-    const size_t n = std::min(total, std::min(m->cap[0], capacity));
-    if (n == 0) return GDP_OK;
-    hipStream_t st = m->side[0]->ctx->stream;
-    GDP_SETTLE(m, "gdp_download_matches", [&](auto&& f) { f(host, n * sizeof(gdp_match_record)); });
-    GDP_HIP(m, hipMemcpyAsync(track_dma_ptr(host), m->d_out, n * sizeof(gdp_match_record), hipMemcpyDeviceToHost, st));
-    GDP_HIP(m, hipStreamSynchronize(st));
-    // the device order depends on the waves' timing; a query yields at most one record
-    std::sort(host, host + n, [](const gdp_match_record& p, const gdp_match_record& q) { return p.query < q.query; });
-    if (stored) *stored = n;
-    return GDP_OK;
-} GDP_MATCH_CATCH(m)
+    return download_sorted(m, "gdp_download_matches", m->d_out, m->d_count, m->cap[0], host, capacity, stored, found);
+} GDP_ABI_CATCH(m)
 
 int gdp_device_matches(const gdp_match* m, const gdp_match_record** records, const uint32_t** count) try {
     if (!m) return GDP_ERR_ARG;

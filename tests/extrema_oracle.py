@@ -2,6 +2,7 @@
 the keypoint rules of include/gdp.h literally, the helpers that compare record sets exactly, the
 pyramid generators, and the "one neighbour decides" lattice pyramids whose keypoints are known in
 closed form, without the oracle.  tests/test_extrema_oracle.py checks the oracle itself on the CPU."""
+import ctypes
 import functools
 
 import numpy as np
@@ -71,6 +72,36 @@ def as_set(kp):
 def assert_sorted(kp):
     keys = [(int(k["octave"]), int(k["scale"]), int(k["row"]), int(k["col"])) for k in kp]
     assert keys == sorted(keys)
+
+
+def assert_short_downloads(download, full, found=True):
+    """`download(host, capacity, stored, found)` calls a stage's gdp_download_* export on a list whose whole
+    sorted download is `full`.  Through a buffer shorter than the list: stored == capacity, found == the
+    full count, and the records are the first `capacity` of `full`.  With host NULL and capacity 0:
+    GDP_OK, nothing stored, found still the full count."""
+    assert len(full) >= 2
+    for capacity in (len(full) - 1, 0):  # one record short: the one left out is the sorted list's last
+        part = np.zeros(len(full), full.dtype)
+        stored, total = ctypes.c_size_t(99), ctypes.c_size_t(99)
+        host = ctypes.c_void_p(part.ctypes.data) if capacity else None
+        assert download(host, capacity, ctypes.byref(stored), ctypes.byref(total)) == 0
+        assert stored.value == capacity and part[:capacity].tobytes() == np.asarray(full)[:capacity].tobytes()
+        assert not part[capacity:].tobytes().strip(b"\0")  # nothing beyond the buffer's capacity
+        assert not found or total.value == len(full)
+
+
+SMALL_IMAGE = (64, 96, 2, 4242)  # H, W, S, seed of the LCG image the list-handling edge cases run on
+
+
+def small_pipeline(pkg, oracle, stages):
+    """A context on the small image, built, with the first `stages` of detect, refine, orient, describe run."""
+    H, W, S, seed = SMALL_IMAGE
+    ctx = pkg.PyramidContext(H, W, S=S)
+    ctx.set_input(oracle.lcg_image(H, W, seed))
+    ctx.build()
+    for run in (ctx.detect_extrema, ctx.refine_keypoints, ctx.orient_keypoints, ctx.describe_keypoints)[:stages]:
+        run()
+    return ctx
 
 
 def packed_size(H, W, S, O):

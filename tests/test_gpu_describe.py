@@ -15,7 +15,8 @@ import numpy as np
 import pytest
 
 from describe_oracle import ORIENTED_DT, as_multiset, assert_download_order, np_describe, oriented_records
-from extrema_oracle import ODD, F, denormal_pyramid, np_extrema, octave_levels, packed_size, smooth_pyramid, tie_pyramid
+from extrema_oracle import (ODD, F, assert_short_downloads, denormal_pyramid, np_extrema, octave_levels, packed_size,
+                            small_pipeline, smooth_pyramid, tie_pyramid)
 from refine_oracle import extrema_records, records_from_set
 
 pytestmark = pytest.mark.gpu
@@ -400,3 +401,19 @@ def test_cpp_example_matches_the_python_path(pkg, oracle):
     for line, k in zip(lines, de):
         assert line == (str(k["octave"]), str(k["scale"]), str(k["row"]), str(k["col"]), "%.4f" % k["angle"], str(k["bin"]),
                         bytes(k["desc"]).hex())
+
+
+# ---------------------------------------------------------------------------------------------
+# 9. the list handling's edges on the small image
+# ---------------------------------------------------------------------------------------------
+def test_short_downloads_and_an_empty_list_then_none(pkg, oracle):
+    L = pkg.lib()
+    with small_pipeline(pkg, oracle, 4) as ctx:
+        full = ctx.described_keypoints(0)
+        assert_short_downloads(lambda *a: L.gdp_download_described(ctx._describe, 0, *a), full)
+        ctx.set_describe_input(np.zeros(0, pkg.ORIENTED_DTYPE))
+        ctx.describe_keypoints()
+        assert ctx.described_count(0) == 0 and len(ctx.described_keypoints(0)) == 0
+        ctx.set_describe_input(None)  # the oriented list again
+        ctx.describe_keypoints()
+        assert ctx.described_keypoints(0).tobytes() == full.tobytes()

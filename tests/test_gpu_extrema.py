@@ -4,7 +4,7 @@ and the bits of the value.  Most cases run on UPLOADED pyramids, independent of 
 import numpy as np
 import pytest
 
-from extrema_oracle import (BIG, ODD, F, as_set, assert_sorted, detect, normal_pyramid, np_extrema, octave_levels,
+from extrema_oracle import (BIG, ODD, F, as_set, assert_short_downloads, assert_sorted, small_pipeline, detect, normal_pyramid, np_extrema, octave_levels,
                             packed_size, smooth_pyramid, tie_pyramid, want)
 
 pytestmark = pytest.mark.gpu
@@ -255,3 +255,9 @@ def test_on_a_bound_output_buffer(pkg):
         off = ctx.level_offset(0, 0, 1)
         assert torch.equal(buf[off:off + 4].cpu(), torch.from_numpy(octave_levels(normal_pyramid(ODD), H, W, S, O)[0][1, 0, :4].copy()))
         ctx.unbind_device_output()
+
+
+def test_download_through_a_short_buffer_and_through_none(pkg, oracle):
+    L = pkg.lib()
+    with small_pipeline(pkg, oracle, 1) as ctx:
+        assert_short_downloads(lambda *a: L.gdp_download_keypoints(ctx._ctx, 0, *a), ctx.keypoints(0))

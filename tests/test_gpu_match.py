@@ -13,7 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from extrema_oracle import ODD, F, smooth_pyramid
+from extrema_oracle import ODD, F, assert_short_downloads, small_pipeline, smooth_pyramid
 from match_oracle import DESCRIBED_DT, MATCH_DT, NONE, distances, np_match
 
 pytestmark = pytest.mark.gpu
@@ -407,3 +407,24 @@ def test_cpp_example_matches_the_python_path(pkg, oracle):
         assert rest in python_lines, rest
     moved = np.count_nonzero((got["tx"] - got["qx"] == F(shift)) & (got["ty"] - got["qy"] == 0))
     print(f"{moved} of {len(got)} kept matches are displaced by exactly ({shift}, 0)")  # reported, not asserted
+
+
+# ---------------------------------------------------------------------------------------------
+# 11. the list handling's edges on the small image: lists just over one 32-record tile
+# ---------------------------------------------------------------------------------------------
+def test_short_downloads_and_an_empty_list_then_none(pkg, oracle):
+    L = pkg.lib()
+    Q, T, D = list_pair(33, 40)
+    with small_pipeline(pkg, oracle, 4) as ctx:
+        before = run(ctx, ratio=0.0)  # both sides read the described list
+        assert len(before) == ctx.described_count(0) > 0
+        ctx.set_match_input(0, Q)
+        ctx.set_match_input(1, T)
+        full = run(ctx, ratio=0.0)
+        assert full.tobytes() == np_match(Q, T, 0.0, D=D).tobytes() and len(full) == 33
+        assert_short_downloads(lambda *a: L.gdp_download_matches(ctx._match, *a), full)
+        ctx.set_match_input(0, Q[:0])
+        assert len(run(ctx, ratio=0.0)) == 0
+        for side in (0, 1):
+            ctx.set_match_input(side, None)  # the described list again
+        assert run(ctx, ratio=0.0).tobytes() == before.tobytes()

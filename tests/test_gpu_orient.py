@@ -12,7 +12,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from extrema_oracle import BIG, ODD, F, denormal_pyramid, normal_pyramid, np_extrema, smooth_pyramid, tie_pyramid
+from extrema_oracle import (BIG, ODD, F, assert_short_downloads, denormal_pyramid, normal_pyramid, np_extrema, small_pipeline,
+                            smooth_pyramid, tie_pyramid)
 from orient_oracle import (DIRECTIONS, as_multiset, assert_download_order, gradient_pyramid, np_orient, refined_from,
                            refined_records)
 from refine_oracle import extrema_records, records_from_set
@@ -322,3 +323,19 @@ def test_cpp_example_matches_the_python_path(pkg, oracle):
     for line, k in zip(lines, ok):
         assert line == (str(k["octave"]), str(k["scale"]), str(k["row"]), str(k["col"]), "%.4f" % k["angle"], str(k["bin"]),
                         str(k["peaks"]))
+
+
+# ---------------------------------------------------------------------------------------------
+# 10. the list handling's edges on the small image
+# ---------------------------------------------------------------------------------------------
+def test_short_downloads_and_an_empty_list_then_none(pkg, oracle):
+    L = pkg.lib()
+    with small_pipeline(pkg, oracle, 3) as ctx:
+        full = ctx.oriented_keypoints(0)
+        assert_short_downloads(lambda *a: L.gdp_download_oriented(ctx._orient, 0, *a), full)
+        ctx.set_orient_input(np.zeros(0, pkg.REFINED_DTYPE))
+        ctx.orient_keypoints()
+        assert ctx.oriented_count(0) == 0 and len(ctx.oriented_keypoints(0)) == 0
+        ctx.set_orient_input(None)  # the refined list again
+        ctx.orient_keypoints()
+        assert ctx.oriented_keypoints(0).tobytes() == full.tobytes()

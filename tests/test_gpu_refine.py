@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from extrema_oracle import (BIG, ODD, F, denormal_pyramid, normal_pyramid, np_extrema, packed_size, smooth_pyramid,
+from extrema_oracle import (BIG, ODD, F, assert_short_downloads, small_pipeline, denormal_pyramid, normal_pyramid, np_extrema, packed_size, smooth_pyramid,
                             tie_pyramid)
 from refine_oracle import (as_multiset, assert_download_order, extrema_records, np_refine, quad_expect, quad_pyramid,
                            records, records_from_set)
@@ -296,3 +296,10 @@ def test_cpp_example_matches_the_python_path(pkg, oracle):
     assert (int(m.group(1)), int(m.group(2))) == (len(kp), len(rf)) and len(kp) > 0
     assert as_multiset(rf) == want_kept
     assert len(re.findall(r"^octave \d+ scale ", out, re.M)) == min(len(rf), 8)
+
+
+def test_download_through_a_short_buffer_and_through_none(pkg, oracle):
+    L = pkg.lib()
+    with small_pipeline(pkg, oracle, 2) as ctx:  # gdp_download_refined has no `found`
+        assert_short_downloads(lambda host, n, stored, _: L.gdp_download_refined(ctx._ctx, 0, host, n, stored),
+                               ctx.refined_keypoints(0), found=False)
