@@ -117,6 +117,17 @@ public:
     // Neither pyramid nor any list is changed; the match object lives for the call only.
     std::vector<gdp_match_record> MatchDescriptors(GaussPyramid_hip& other, float ratio = 0.8f,
                                                    uint32_t max_distance = 0xffffffffu, bool mutual = false);
+    // Extension: the homography that most of `matches` (MatchDescriptors' records, in the order given)
+    // agree on, by RANSAC on the device (gdp_fit_homography in gdp.h has the exact rule: `hypotheses`
+    // four-point fits in float64 without a division, each scored in float32 against every match with
+    // the transfer error `threshold` in pixels; the largest count wins, ties to the lowest index).
+    // Returns the model record: h[] maps (qx, qy, 1) to (tx, ty, 1) up to scale; hypothesis ==
+    // 0xffffffff when fewer than max(min_inliers, 4) matches agree.  *inliers (when not NULL) gets
+    // the matches the model accepts, sorted by `query`.  The list is the caller's, so the result is
+    // a function of the arguments alone.  Nothing of the pyramid or its lists is changed; the fit
+    // object lives for the call only.
+    gdp_homography FitHomography(const std::vector<gdp_match_record>& matches, std::vector<gdp_match_record>* inliers = nullptr,
+                                 uint32_t hypotheses = 1024, uint32_t seed = 0, float threshold = 3.0f, uint32_t min_inliers = 4);
     ~GaussPyramid_hip();
     bool initialized;
     bool mirror_host;  // GaussPy two-way: upload before / download after every mutating call (default true)
@@ -493,6 +504,38 @@ inline std::vector<gdp_match_record> GaussPyramid_hip::MatchDescriptors(GaussPyr
     out.resize(stored);
     gdp_match_destroy(m);
     return out;
+}
+
+inline gdp_homography GaussPyramid_hip::FitHomography(const std::vector<gdp_match_record>& matches, std::vector<gdp_match_record>* inliers,
+                                                      uint32_t hypotheses, uint32_t seed, float threshold, uint32_t min_inliers) {
+    auto check = [](const char* last, int status) {
+        if (status != GDP_OK) {
+            std::fprintf(stderr, "GaussPyramid_hip::FitHomography failed: %s (%s)\n", gdp_status_string(status), last);
+            std::abort();
+        }
+    };
+    if (!orient_) check(gdp_orient_last_error(nullptr), gdp_orient_create(&orient_, ctx_, 0));
+    if (!describe_) check(gdp_describe_last_error(nullptr), gdp_describe_create(&describe_, ctx_, orient_, 0));
+    const size_t n = matches.size(), cap = n ? n : 1;
+    gdp_match* m = nullptr;  // the fit object is made from a match object; its own list is never read here
+    check(gdp_match_last_error(nullptr), gdp_match_create(&m, describe_, describe_, cap, 1));
+    gdp_ransac* r = nullptr;
+    check(gdp_ransac_last_error(nullptr), gdp_ransac_create(&r, m, cap, hypotheses));
+    const gdp_match_record none{};
+    check(gdp_ransac_last_error(r), gdp_ransac_set_input(r, n ? matches.data() : &none, n));
+    check(gdp_ransac_last_error(r), gdp_fit_homography(r, hypotheses, seed, threshold, min_inliers, nullptr));
+    gdp_homography model;
+    check(gdp_ransac_last_error(r), gdp_download_homography(r, &model));
+    if (inliers) {
+        size_t found = 0, stored = 0;
+        check(gdp_ransac_last_error(r), gdp_ransac_count(r, &found));
+        inliers->resize(found);
+        check(gdp_ransac_last_error(r), gdp_download_inliers(r, inliers->data(), inliers->size(), &stored, nullptr));
+        inliers->resize(stored);
+    }
+    gdp_ransac_destroy(r);
+    gdp_match_destroy(m);
+    return model;
 }
 
 inline void GaussPyramid_hip::output() {  // :89-104

@@ -624,6 +624,118 @@ int gdp_device_matches(const gdp_match* m, const gdp_match_record** records, con
 int gdp_match_layout(const gdp_match* m, size_t* query_capacity, size_t* train_capacity, uint32_t* chunk_unit,
                      uint32_t* train_chunks, uint32_t* query_chunks);
 
+/* ---- extension: RANSAC homography of the matches on the device ---------------------------------
+ * What the matches' coordinates are for: which matches are geometrically consistent, and under which
+ * projective transform (no reference counterpart, no parity claim).  H hypotheses, each the exact
+ * homography of four sampled matches, are scored against every match; the best one is the model and
+ * the matches it accepts are the inliers.  It writes nothing of a context, an orientation, describe
+ * or match object: its state is an object of its own, gdp_ransac, created from a const gdp_match.
+ *
+ * The rule.  Input is a list M[0..n) of gdp_match_record, of which only qx, qy, tx, ty are read; the
+ * parameters are `hypotheses` H, `seed`, `threshold` t and `min_inliers`.
+ *   1 sample        (integers only.)  mix(x) on uint32 with wrap-around:  x ^= x >> 16;
+ *                   x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16.  For hypothesis
+ *                   h < H and slot k < 4:  r = mix(seed + 0x9e3779b9 * (4h + k + 1))  and
+ *                   sample[k] = ((uint64)r * n) >> 32.  A hypothesis is VALID only when n >= 4 and
+ *                   its four indices are pairwise distinct; there is no resampling loop
+ *   2 basis         (float64, every operation separately rounded, no contraction.)  The four query
+ *                   points, converted exactly to double, are p_k = (x_k, y_k, 1), and Mq = [p0 p1 p2]
+ *                   has them as its COLUMNS: Mq[0][c] = x_c, Mq[1][c] = y_c, Mq[2][c] = 1.  adj(M) is
+ *                   nine expressions, each two rounded products and one rounded difference:
+ *                     adj[0][0] = M[1][1] * M[2][2] - M[1][2] * M[2][1]
+ *                     adj[0][1] = M[0][2] * M[2][1] - M[0][1] * M[2][2]
+ *                     adj[0][2] = M[0][1] * M[1][2] - M[0][2] * M[1][1]
+ *                     adj[1][0] = M[1][2] * M[2][0] - M[1][0] * M[2][2]
+ *                     adj[1][1] = M[0][0] * M[2][2] - M[0][2] * M[2][0]
+ *                     adj[1][2] = M[0][2] * M[1][0] - M[0][0] * M[1][2]
+ *                     adj[2][0] = M[1][0] * M[2][1] - M[1][1] * M[2][0]
+ *                     adj[2][1] = M[0][1] * M[2][0] - M[0][0] * M[2][1]
+ *                     adj[2][2] = M[0][0] * M[1][1] - M[0][1] * M[1][0]
+ *                   lambda = adj(Mq) * p3:  lambda[r] = (adj[r][0] * x3 + adj[r][1] * y3) + adj[r][2];
+ *                   A[r][c] = Mq[r][c] * lambda[c].  The same from the four train points gives B.  No
+ *                   division and no pivoting anywhere
+ *   3 compose       (float64.)  J = adj(A) as above;
+ *                   G[r][c] = (B[r][0] * J[0][c] + B[r][1] * J[1][c]) + B[r][2] * J[2][c]
+ *   4 normalise     s = max |G[r][c]|.  If s is 0, infinite or NaN, or any entry is NaN, the hypothesis
+ *                   is INVALID.  Otherwise s = m * 2^e with m in [0.5, 1) (frexp) and G <- ldexp(G, -e);
+ *                   w0 = (G[2][0] * x0 + G[2][1] * y0) + G[2][2] at query sample 0, in double; if
+ *                   w0 < 0, G is negated;  h[3r + c] = (float)G[r][c], round to nearest even, float32
+ *                   denormals kept (so max |h| lies in [0.5, 1]: a value just below 1 may round to 1).
+ *                   An invalid hypothesis has h[] = 0 and counts nothing; its sample[] is stored all
+ *                   the same
+ *   5 score         (float32, every operation separately rounded.)  For match i = (x, y, X, Y):
+ *                     u = (h0 * x + h1 * y) + h2,  v = (h3 * x + h4 * y) + h5,  w = (h6 * x + h7 * y) + h8,
+ *                     dx = X * w - u,  dy = Y * w - v,  e = dx * dx + dy * dy;
+ *                   an inlier when  w > 0  and  e <= (t * t) * (w * w).  No division; NaN coordinates fail
+ *                   both comparisons.  The hypothesis's count is the number of inliers among i < n, an
+ *                   exact integer
+ *   6 select        the winner is the valid hypothesis with the largest count, ties to the lowest h.  A
+ *                   model exists iff a winner exists and its count >= max(min_inliers, 4)
+ *   7 inliers       the records of M that step 5 accepts under the winner's h[], copied unchanged; the
+ *                   empty list when no model exists
+ *   8 addresses     nothing but the four floats is read from a record, and no address is formed from
+ *                   record contents: any 32 bytes are a valid record
+ * Every quantity is a function of the list in the order the kernel read it, the seed and the
+ * parameters, and the counts are integer sums, so the result is an exact set, independent of tiling
+ * and wave timing.  For a list the pipeline produced (the match object's) that order is the device
+ * order (gdp_device_matches), which is unspecified, as with `query` / `train` of the matches; for a
+ * list the caller supplied (gdp_ransac_set_input) it is exactly the caller's.  Out of scope:
+ * least-squares refinement over the inliers, early termination, other models. */
+typedef struct gdp_homography {   /* 64 bytes, four 16-B stores */
+    float    h[9];                /* row-major, as scored: max |h| in [0.5, 1]; all 0 = invalid / none */
+    uint32_t hypothesis;          /* its index; 0xffffffff in the model record when there is none */
+    uint32_t inliers;             /* step 5's count (0 in a model record without a model) */
+    uint32_t matches;             /* the n this launch read */
+    uint32_t sample[4];           /* step 1's indices; 0xffffffff in a model record without a model */
+} gdp_homography;
+typedef struct gdp_ransac gdp_ransac;
+/* A fit object reading one match object (non-NULL), which is only read — its list and counter are
+ * looked up at every launch — and must outlive this object: destroy this one first.  `capacity` is
+ * the longest list a fit reads (0: the match object's query capacity; at most 2^30), max_hypotheses
+ * the most hypotheses of one fit (0: 4,096; above 65,536 is GDP_ERR_ARG).  The object owns the
+ * hypothesis records, an inlier buffer of `capacity` records (so it cannot overflow), the model
+ * record, one uint32 counter and the caller's list.  gdp_ransac_last_error(r) describes r's last
+ * failure (r NULL: this thread's last failed create). */
+int gdp_ransac_create(gdp_ransac** out, const gdp_match* src, size_t capacity, uint32_t max_hypotheses);
+void gdp_ransac_destroy(gdp_ransac* r);
+const char* gdp_ransac_last_error(const gdp_ransac* r);
+/* Make host[0..n) the list instead of the match object's (blocking): n must not exceed the capacity,
+ * else GDP_ERR_ARG and nothing changes.  Records are not validated (point 8 of the rule).  An empty
+ * list (host non-NULL, n = 0) is a list; host = NULL goes back to the match object's list. */
+int gdp_ransac_set_input(gdp_ransac* r, const gdp_match_record* host, size_t n);
+/* Fit: zeroes the counter on `stream` (NULL = the query context's own stream), then launches;
+ * asynchronous and stream-ordered.  Without a list of the caller's it reads the first min(counter,
+ * the match object's query capacity, this object's capacity) records of the match object's output;
+ * the count is read on the device, the host never reads it, so launching this right after
+ * gdp_match_descriptors on the same stream is the normal use.  `hypotheses` must be in
+ * 1..max_hypotheses and `threshold` finite and >= 0 (a NaN included), else GDP_ERR_ARG and nothing
+ * changes: the previous fit's results stay downloadable. */
+int gdp_fit_homography(gdp_ransac* r, uint32_t hypotheses, uint32_t seed, float threshold,
+                       uint32_t min_inliers, void* stream);
+/* Inliers of the last fit (blocking; waits for the query context's OWN stream; 0 before any). */
+int gdp_ransac_count(gdp_ransac* r, size_t* inliers);
+/* The model record of the last fit (blocking): the winner's record, or h[] = 0, hypothesis =
+ * 0xffffffff, inliers = 0, matches = n, sample[] = 0xffffffff when there is no model (matches = 0
+ * before any fit). */
+int gdp_download_homography(gdp_ransac* r, gdp_homography* model);
+/* Records 0 .. H-1 of the last fit, in index order, as many as fit into `capacity` (blocking).
+ * *stored = records written (may be NULL); 0 before any fit. */
+int gdp_download_hypotheses(gdp_ransac* r, gdp_homography* host, size_t capacity, size_t* stored);
+/* Copy min(found, `capacity`) inlier records to `host` (blocking), sorted ascending by `query`; a
+ * buffer shorter than the list takes the head of the full sorted list.  *stored = records written,
+ * *found = gdp_ransac_count (either may be NULL). */
+int gdp_download_inliers(gdp_ransac* r, gdp_match_record* host, size_t capacity, size_t* stored, size_t* found);
+/* Zero-copy view for device consumers (any output may be NULL): the inlier records (`capacity`
+ * records, the first *count valid, device order), the counter and the model record. */
+int gdp_device_inliers(const gdp_ransac* r, const gdp_match_record** records, const uint32_t** count,
+                       const gdp_homography** model);
+/* How the object cuts the work (any output may be NULL): its capacity and max_hypotheses; the chunk
+ * granule of the match list (the scoring sweep cuts a list of n records into c chunks at multiples of
+ * ceil(ceil(n / c) / granule) * granule, computed on the device from the count it reads); and the
+ * hypotheses per block of the scoring sweep, one per lane. */
+int gdp_ransac_layout(const gdp_ransac* r, size_t* capacity, uint32_t* max_hypotheses,
+                      uint32_t* match_tile, uint32_t* hypothesis_tile);
+
 /* ---- output --------------------------------------------------------------------------------
  * The blocking copies below are ordered after work on the context's OWN stream; if a build was
  * launched on another stream, synchronize that stream first. */

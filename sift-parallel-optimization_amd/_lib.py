@@ -155,6 +155,18 @@ SIGNATURES = {
     "gdp_device_matches": (_c_int, [_p, _pp, _pp]),
     "gdp_match_layout": (_c_int, [_p, ctypes.POINTER(_c_size), ctypes.POINTER(_c_size), ctypes.POINTER(_c_u32),
                                   ctypes.POINTER(_c_u32), ctypes.POINTER(_c_u32)]),
+    "gdp_ransac_create": (_c_int, [_pp, _p, _c_size, _c_u32]),
+    "gdp_ransac_destroy": (None, [_p]),
+    "gdp_ransac_last_error": (ctypes.c_char_p, [_p]),
+    "gdp_ransac_set_input": (_c_int, [_p, _p, _c_size]),
+    "gdp_fit_homography": (_c_int, [_p, _c_u32, _c_u32, ctypes.c_float, _c_u32, _p]),
+    "gdp_ransac_count": (_c_int, [_p, ctypes.POINTER(_c_size)]),
+    "gdp_download_homography": (_c_int, [_p, _p]),
+    "gdp_download_hypotheses": (_c_int, [_p, _p, _c_size, ctypes.POINTER(_c_size)]),
+    "gdp_download_inliers": (_c_int, [_p, _p, _c_size, ctypes.POINTER(_c_size), ctypes.POINTER(_c_size)]),
+    "gdp_device_inliers": (_c_int, [_p, _pp, _pp, _pp]),
+    "gdp_ransac_layout": (_c_int, [_p, ctypes.POINTER(_c_size), ctypes.POINTER(_c_u32), ctypes.POINTER(_c_u32),
+                                   ctypes.POINTER(_c_u32)]),
     "gdp_checksum": (_c_int, [_p, _c_int, ctypes.POINTER(ctypes.c_uint64)]),
     "gdp_get_taps": (_c_int, [_p, _c_int, _c_int, _c_int, _p]),
     "gdp_set_window_centre": (_c_int, [_p, _c_int]),
@@ -217,13 +229,15 @@ def build_variants():
     return list(ids)
 
 
-def check(status, ctx=None, orient=False, describe=False, match=False):
+def check(status, ctx=None, orient=False, describe=False, match=False, ransac=False):
     """Raise GdpError for a non-zero status; `ctx` is the context whose gdp_last_error describes it
-    (orient=True: a gdp_orient object, or None for a failed gdp_orient_create; describe=True and
-    match=True: the same for a gdp_describe and a gdp_match object)."""
+    (orient=True: a gdp_orient object, or None for a failed gdp_orient_create; describe=True,
+    match=True and ransac=True: the same for a gdp_describe, a gdp_match and a gdp_ransac object)."""
     if status != GDP_OK:
         L = lib()
-        if match:
+        if ransac:
+            msg = L.gdp_ransac_last_error(ctx)
+        elif match:
             msg = L.gdp_match_last_error(ctx)
         else:
             msg = L.gdp_describe_last_error(ctx) if describe else L.gdp_orient_last_error(ctx) if orient else L.gdp_last_error(ctx)

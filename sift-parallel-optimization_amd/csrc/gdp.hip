@@ -59,6 +59,7 @@ namespace {
 #include "gdp_orient.inc"
 #include "gdp_describe.inc"
 #include "gdp_match.inc"
+#include "gdp_ransac.inc"
 #include "gdp_util.inc"
 #include "gdp_track.inc"
 
@@ -277,6 +278,22 @@ struct gdp_match : ErrorState {
     uint4* d_part[2] = {nullptr, nullptr};     // [chunks[0]][pad[0]] and [chunks[1]][pad[1]] partial triples
     gdp_keypoint_described* d_in[2] = {nullptr, nullptr};  // the caller's lists, allocated on first use
     uint32_t* d_in_count = nullptr;            // [2]: their lengths; kMaNoList = the describe object's list
+};
+
+// gdp_ransac_create: the homography fit's state.  It reads one gdp_match object (its list and counter,
+// looked up at every launch, never written) and owns everything it writes.
+struct gdp_ransac : ErrorState {
+    const gdp_match* src = nullptr;
+    int device = 0;                        // the match object's device
+    size_t capacity = 0;                   // records a list may hold; also the inlier buffer's capacity
+    uint32_t max_hypotheses = 0;
+    uint32_t hypotheses = 0;               // H of the last fit: what gdp_download_hypotheses reports
+    gdp_homography* d_hyp = nullptr;       // [max_hypotheses]
+    gdp_homography* d_model = nullptr;     // the model record ("none" until a fit finds one)
+    gdp_match_record* d_out = nullptr;     // [capacity]: the inliers
+    uint32_t* d_count = nullptr;           // one counter
+    gdp_match_record* d_in = nullptr;      // the caller's list, allocated on first use
+    uint32_t* d_in_count = nullptr;        // its length; kRaNoList = the match object's list
 };
 
 namespace {
@@ -776,10 +793,11 @@ const gdp_ctx* ctx_of(const gdp_ctx* c) { return c; }
 const gdp_ctx* ctx_of(const gdp_orient* w) { return w->ctx; }
 const gdp_ctx* ctx_of(const gdp_describe* w) { return w->ctx; }
 const gdp_ctx* ctx_of(const gdp_match* m) { return m->side[0]->ctx; }
+const gdp_ctx* ctx_of(const gdp_ransac* r) { return ctx_of(r->src); }
 
 // d_in_count of a slot that reads its producer's list, not the caller's
 constexpr uint32_t kNoList = 0xffffffffu;
-static_assert(kOrNoList == kNoList && kDeNoList == kNoList && kMaNoList == kNoList, "one sentinel, filled bytewise (0xff)");
+static_assert(kOrNoList == kNoList && kDeNoList == kNoList && kMaNoList == kNoList && kRaNoList == kNoList, "one sentinel, filled bytewise (0xff)");
 
 // element i of a device array that may not be allocated yet
 template <class T>
@@ -3495,6 +3513,151 @@ int gdp_device_matches(const gdp_match* m, const gdp_match_record** records, con
     if (!m) return GDP_ERR_ARG;
     if (records) *records = m->d_out;
     if (count) *count = m->d_count;
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+// ---- extension: RANSAC homography of the matches (gdp_ransac.inc) ----------------------------------
+// No export below takes a mutable context, orientation, describe or match object: the state is the
+// gdp_ransac object's, the match object is read (k_ransac_* take its list const).
+
+static_assert(sizeof(gdp_homography) == 64 && sizeof(gdp_match_record) == 32, "four and two 16-byte stores");
+
+void gdp_ransac_destroy(gdp_ransac* r) {
+    if (!r) return;
+    (void)hipSetDevice(r->device);
+    (void)hipDeviceSynchronize();  // a launch on any stream may still read or write the buffers
+    if (r->d_hyp) (void)hipFree(r->d_hyp);
+    if (r->d_model) (void)hipFree(r->d_model);
+    if (r->d_out) (void)hipFree(r->d_out);
+    if (r->d_count) (void)hipFree(r->d_count);
+    if (r->d_in) (void)hipFree(r->d_in);
+    if (r->d_in_count) (void)hipFree(r->d_in_count);
+    delete r;
+}
+
+int gdp_ransac_create(gdp_ransac** out, const gdp_match* src, size_t capacity, uint32_t max_hypotheses) try {
+    if (!out || !src) return GDP_ERR_ARG;
+    if (capacity == 0) capacity = src->cap[0];
+    if (max_hypotheses == 0) max_hypotheses = kRaDefaultHypotheses;
+    if (capacity > (1ull << 30)) return create_fail(GDP_ERR_ARG, "gdp_ransac_create: a capacity above 2^30 records");
+    if (max_hypotheses > kRaMaxHypotheses) return create_fail(GDP_ERR_ARG, "gdp_ransac_create: more than 65,536 hypotheses");
+    hipError_t e = hipSetDevice(src->device);
+    if (e != hipSuccess) return create_fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    gdp_ransac* r = new gdp_ransac;
+    r->src = src;
+    r->device = src->device;
+    r->capacity = capacity;
+    r->max_hypotheses = max_hypotheses;
+    e = hipMalloc(reinterpret_cast<void**>(&r->d_hyp), (size_t)max_hypotheses * sizeof(gdp_homography));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&r->d_model), sizeof(gdp_homography));
+    if (e == hipSuccess) {  // no model before the first fit
+        gdp_homography none{};
+        none.hypothesis = kRaNone;
+        for (uint32_t& s : none.sample) s = kRaNone;
+        e = hipMemcpy(r->d_model, &none, sizeof none, hipMemcpyHostToDevice);
+    }
+    return finish_create(out, r, gdp_ransac_destroy, "gdp_ransac_create", 1, e);
+} GDP_ABI_CATCH(nullptr)
+
+const char* gdp_ransac_last_error(const gdp_ransac* r) { return r ? r->err.c_str() : g_create_error.c_str(); }
+
+int gdp_ransac_layout(const gdp_ransac* r, size_t* capacity, uint32_t* max_hypotheses, uint32_t* match_tile,
+                      uint32_t* hypothesis_tile) try {
+    if (!r) return GDP_ERR_ARG;
+    if (capacity) *capacity = r->capacity;
+    if (max_hypotheses) *max_hypotheses = r->max_hypotheses;
+    if (match_tile) *match_tile = kRaMatchTile;
+    if (hypothesis_tile) *hypothesis_tile = kRaHypTile;
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+int gdp_ransac_set_input(gdp_ransac* r, const gdp_match_record* host, size_t n) try {
+    if (!r) return GDP_ERR_ARG;
+    if (host && n > r->capacity)
+        return r->status(GDP_ERR_ARG, "gdp_ransac_set_input: %zu records exceed the capacity %zu", n, r->capacity);
+    // nothing is validated per record: the kernels read qx, qy, tx and ty as data and form no address from them
+    return replace_input(r, "gdp_ransac_set_input", &r->d_in, r->capacity, 0, r->d_in_count, host, n,
+                         [](size_t, const gdp_match_record&) { return (int)GDP_OK; });
+} GDP_ABI_CATCH(r)
+
+int gdp_fit_homography(gdp_ransac* r, uint32_t hypotheses, uint32_t seed, float threshold, uint32_t min_inliers,
+                       void* stream) try {
+    if (!r) return GDP_ERR_ARG;
+    if (hypotheses == 0 || hypotheses > r->max_hypotheses)
+        return r->status(GDP_ERR_ARG, "gdp_fit_homography: %u hypotheses are not in 1..%u", hypotheses, r->max_hypotheses);
+    if (!(threshold >= 0.0f && std::isfinite(threshold)))  // a NaN fails the first
+        return r->status(GDP_ERR_ARG, "gdp_fit_homography: threshold %g is not finite and >= 0", (double)threshold);
+    const gdp_match* m = r->src;
+    RaList list;
+    list.src = reinterpret_cast<const uint4*>(m->d_out);
+    list.src_count = m->d_count;
+    list.src_cap = (unsigned)std::min(m->cap[0], r->capacity);
+    list.own = reinterpret_cast<const uint4*>(r->d_in);
+    list.own_count = r->d_in_count;
+    GDP_HIP(r, hipSetDevice(r->device));
+    hipStream_t st = ctx_of(r)->pick(stream);
+    const float tt = threshold * threshold;  // one rounded float32 product
+    // chunks of the match list: enough for kRaTargetWaves waves with this H, never shorter than kRaMatchTile records
+    const unsigned hyp_blocks = (hypotheses + kRaHypTile - 1) / kRaHypTile;
+    const size_t most = std::max<size_t>(1, (r->capacity + kRaMatchTile - 1) / kRaMatchTile);
+    const unsigned chunks = (unsigned)std::min<size_t>(most, (kRaTargetWaves + hyp_blocks * 4 - 1) / (hyp_blocks * 4));
+    GDP_HIP(r, hipMemsetAsync(r->d_count, 0, sizeof(uint32_t), st));
+    r->hypotheses = hypotheses;
+    hipLaunchKernelGGL(k_ransac_fit, dim3(hyp_blocks), dim3(kRaHypTile), 0, st, list, hypotheses, seed,
+                       reinterpret_cast<uint4*>(r->d_hyp));
+    hipLaunchKernelGGL(k_ransac_score, dim3(hyp_blocks, chunks), dim3(kRaHypTile), 0, st, list, hypotheses, tt, chunks,
+                       reinterpret_cast<uint32_t*>(r->d_hyp));
+    hipLaunchKernelGGL(k_ransac_select, dim3(1), dim3(1024), 0, st, list, hypotheses, min_inliers,
+                       reinterpret_cast<const uint4*>(r->d_hyp), reinterpret_cast<uint4*>(r->d_model));
+    hipLaunchKernelGGL(k_ransac_inliers, dim3((unsigned)((r->capacity + 255) / 256)), dim3(256), 0, st, list, tt,
+                       reinterpret_cast<const uint4*>(r->d_model), reinterpret_cast<uint4*>(r->d_out), r->d_count);
+    GDP_HIP(r, hipGetLastError());
+    return GDP_OK;
+} GDP_ABI_CATCH(r)
+
+int gdp_ransac_count(gdp_ransac* r, size_t* inliers) try {
+    if (!r || !inliers) return r ? r->status(GDP_ERR_ARG, "gdp_ransac_count: bad argument") : GDP_ERR_ARG;
+    return read_counter(r, r->d_count, inliers);
+} GDP_ABI_CATCH(r)
+
+// `n` records from the device after the work on the context's own stream (blocking)
+static int ransac_records(gdp_ransac* r, const char* who, const gdp_homography* d_recs, gdp_homography* host, size_t n) {
+    const gdp_ctx* c = ctx_of(r);
+    GDP_HIP(r, hipSetDevice(c->device));
+    GDP_SETTLE(r, who, [&](auto&& f) { f(host, n * sizeof(gdp_homography)); });
+    GDP_HIP(r, hipMemcpyAsync(track_dma_ptr(host), d_recs, n * sizeof(gdp_homography), hipMemcpyDeviceToHost, c->stream));
+    GDP_HIP(r, hipStreamSynchronize(c->stream));
+    return GDP_OK;
+}
+
+int gdp_download_homography(gdp_ransac* r, gdp_homography* model) try {
+    if (!r || !model) return r ? r->status(GDP_ERR_ARG, "gdp_download_homography: bad argument") : GDP_ERR_ARG;
+    return ransac_records(r, "gdp_download_homography", r->d_model, model, 1);
+} GDP_ABI_CATCH(r)
+
+int gdp_download_hypotheses(gdp_ransac* r, gdp_homography* host, size_t capacity, size_t* stored) try {
+    if (!r) return GDP_ERR_ARG;
+    if (!host && capacity) return r->status(GDP_ERR_ARG, "gdp_download_hypotheses: bad argument");
+    if (stored) *stored = 0;
+    const size_t n = std::min<size_t>(r->hypotheses, capacity);
+    if (n == 0) return GDP_OK;
+    const int rc = ransac_records(r, "gdp_download_hypotheses", r->d_hyp, host, n);
+    if (rc == GDP_OK && stored) *stored = n;
+    return rc;
+} GDP_ABI_CATCH(r)
+
+int gdp_download_inliers(gdp_ransac* r, gdp_match_record* host, size_t capacity, size_t* stored, size_t* found) try {
+    if (!r) return GDP_ERR_ARG;
+    if (!host && capacity) return r->status(GDP_ERR_ARG, "gdp_download_inliers: bad argument");
+    return download_sorted(r, "gdp_download_inliers", r->d_out, r->d_count, r->capacity, host, capacity, stored, found);
+} GDP_ABI_CATCH(r)
+
+int gdp_device_inliers(const gdp_ransac* r, const gdp_match_record** records, const uint32_t** count,
+                       const gdp_homography** model) try {
+    if (!r) return GDP_ERR_ARG;
+    if (records) *records = r->d_out;
+    if (count) *count = r->d_count;
+    if (model) *model = r->d_model;
     return GDP_OK;
 } GDP_ABI_CATCH(nullptr)
 

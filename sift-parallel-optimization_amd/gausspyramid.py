@@ -87,6 +87,20 @@ MATCH_DTYPE = np.dtype({"names": ["query", "train", "distance", "second", "qx", 
                         "formats": [np.uint32, np.uint32, np.uint32, np.uint32, np.float32, np.float32, np.float32, np.float32],
                         "offsets": [0, 4, 8, 12, 16, 20, 24, 28], "itemsize": 32})
 
+# struct gdp_homography (include/gdp.h): 64 bytes
+HOMOGRAPHY_DTYPE = np.dtype({"names": ["h", "hypothesis", "inliers", "matches", "sample"],
+                             "formats": [(np.float32, (9,)), np.uint32, np.uint32, np.uint32, (np.uint32, (4,))],
+                             "offsets": [0, 36, 40, 44, 48], "itemsize": 64})
+
+
+class Homography(np.ndarray):
+    """One HOMOGRAPHY_DTYPE record (0-d) with `matrix`: its 3 x 3 float32 array, row-major as scored,
+    or None when the record holds no model."""
+
+    @property
+    def matrix(self):
+        return None if int(self["hypothesis"]) == 0xffffffff else np.array(self["h"], np.float32).reshape(3, 3)
+
 
 class Keypoints(np.ndarray):
     """A KEYPOINT_DTYPE array of the stored records with `found`, the number the detection counted
@@ -729,6 +743,7 @@ class PyramidContext:
         return self._match_handle(self._match_train() if m is not None and m.value else None)
 
     def _drop_match(self):
+        self._drop_ransac()  # it reads the match object: it goes first
         m = getattr(self, "_match", None)
         if m is not None and m.value:
             lib().gdp_match_destroy(m)
@@ -804,6 +819,113 @@ class PyramidContext:
         check(lib().gdp_match_layout(m, ctypes.byref(qc), ctypes.byref(tc), ctypes.byref(unit), ctypes.byref(tch), ctypes.byref(qch)),
               m, match=True)
         return qc.value, tc.value, unit.value, tch.value, qch.value
+
+    # ------------------------------------------------------------------ RANSAC homography (extension)
+    def _ransac_handle(self):
+        """The gdp_ransac object that reads this context's current match object, created on first
+        use and again whenever the match object is (it is dropped before the match object it reads)."""
+        m = self._match_current()
+        r = getattr(self, "_ransac", None)
+        if r is not None and r.value and self._ransac_of == m.value:
+            return r
+        self._drop_ransac()
+        r = ctypes.c_void_p()
+        n, hyp = getattr(self, "_ransac_capacity", (0, 0))
+        check(lib().gdp_ransac_create(ctypes.byref(r), m, int(n), int(hyp)), None, ransac=True)
+        self._ransac, self._ransac_of = r, m.value
+        return r
+
+    def _drop_ransac(self):
+        r = getattr(self, "_ransac", None)
+        if r is not None and r.value:
+            lib().gdp_ransac_destroy(r)
+            self._ransac = ctypes.c_void_p()
+
+    def set_ransac_capacity(self, n=0, max_hypotheses=0):
+        """The longest list a fit reads, which is also the most inliers kept (0: the match object's
+        query capacity), and the most hypotheses of one fit (0: 4,096; at most 65,536).  Drops the
+        earlier results and the input list."""
+        if int(n) < 0 or int(max_hypotheses) < 0:
+            raise ValueError("a RANSAC capacity must be >= 0")
+        self._drop_ransac()
+        self._ransac_capacity = (int(n), int(max_hypotheses))
+
+    def fit_homography(self, hypotheses=1024, seed=0, threshold=3.0, min_inliers=4, stream=None):
+        """Fit a homography to the last match's records (or set_ransac_input's) on the device
+        (gdp_fit_homography: `hypotheses` four-point homographies in float64 without a division,
+        each scored in float32 against every match with the transfer error `threshold` in pixels,
+        the largest count wins, ties to the lowest index); asynchronous on `stream`, no host read of
+        the match counter."""
+        r = self._ransac_handle()
+        check(lib().gdp_fit_homography(r, int(hypotheses), int(seed) & 0xffffffff, float(threshold), int(min_inliers),
+                                       _stream_handle(stream)), r, ransac=True)
+
+    def set_ransac_input(self, recs):
+        """Make `recs` (MATCH_DTYPE) the list a fit reads instead of the match object's (blocking;
+        records are not validated: any 32 bytes are a record); None goes back to the match object's."""
+        r = self._ransac_handle()
+        if recs is None:
+            check(lib().gdp_ransac_set_input(r, None, 0), r, ransac=True)
+            return
+        recs = np.ascontiguousarray(recs, dtype=MATCH_DTYPE).reshape(-1)
+        keep = recs if recs.size else np.zeros(1, MATCH_DTYPE)  # an empty list is still a list: a non-null pointer
+        check(lib().gdp_ransac_set_input(r, _ptr(keep), recs.size), r, ransac=True)
+
+    def homography(self):
+        """The last fit's model record (blocking) as a Homography: its `matrix` is the 3 x 3 float32
+        array, or None when there is no model (hypothesis = 0xffffffff)."""
+        r = self._ransac_handle()
+        out = np.zeros(1, HOMOGRAPHY_DTYPE)
+        check(lib().gdp_download_homography(r, _ptr(out)), r, ransac=True)
+        return out[0:1].reshape(()).view(Homography)
+
+    def hypotheses(self):
+        """Every hypothesis record of the last fit as a HOMOGRAPHY_DTYPE array in index order (blocking)."""
+        r = self._ransac_handle()
+        _, most, _, _ = self.ransac_layout()
+        out = np.zeros(most, HOMOGRAPHY_DTYPE)
+        stored = ctypes.c_size_t()
+        check(lib().gdp_download_hypotheses(r, _ptr(out), out.size, ctypes.byref(stored)), r, ransac=True)
+        return out[:stored.value]
+
+    def inlier_count(self):
+        """Inliers of the last fit (blocking; 0 before any and without a model)."""
+        r = getattr(self, "_ransac", None)
+        if r is None or not r.value:
+            return 0
+        n = ctypes.c_size_t()
+        check(lib().gdp_ransac_count(r, ctypes.byref(n)), r, ransac=True)
+        return n.value
+
+    def inliers(self):
+        """The last fit's inlier records as a MATCH_DTYPE array sorted by `query` (blocking); its
+        `found` attribute is inlier_count()."""
+        r = getattr(self, "_ransac", None)
+        if r is None or not r.value:
+            return np.zeros(0, MATCH_DTYPE).view(Keypoints)
+        out = np.zeros(self.inlier_count(), MATCH_DTYPE)
+        stored, found = ctypes.c_size_t(), ctypes.c_size_t()
+        check(lib().gdp_download_inliers(r, _ptr(out) if out.size else None, out.size, ctypes.byref(stored), ctypes.byref(found)),
+              r, ransac=True)
+        out = out[:stored.value].view(Keypoints)
+        out.found = found.value
+        return out
+
+    def device_inliers(self):
+        """(device address of the inlier records, of their uint32 counter, of the model record)."""
+        r = self._ransac_handle()
+        recs, count, model = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        check(lib().gdp_device_inliers(r, ctypes.byref(recs), ctypes.byref(count), ctypes.byref(model)), r, ransac=True)
+        return recs.value, count.value, model.value
+
+    def ransac_layout(self):
+        """(capacity, max hypotheses, match chunk granule, hypotheses per block) of the fit object
+        (gdp_ransac_layout)."""
+        r = self._ransac_handle()
+        cap = ctypes.c_size_t()
+        most, mt, ht = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        check(lib().gdp_ransac_layout(r, ctypes.byref(cap), ctypes.byref(most), ctypes.byref(mt), ctypes.byref(ht)), r, ransac=True)
+        return cap.value, most.value, mt.value, ht.value
 
     def device_level_ptr(self, b, o, s):
         """Device address of level (o, s) of image b.  Read-only: after writing through it, call
@@ -974,6 +1096,15 @@ class GaussPyramid:
         Neither pyramid nor any list is changed."""
         self._ctx.match_descriptors(None if other is None else other._ctx, 0, 0, ratio, max_distance, mutual)
         return self._ctx.matches()
+
+    def FitHomography(self, matches=None, hypotheses=1024, seed=0, threshold=3.0, min_inliers=4):
+        """Extension: fit a homography to `matches` (MATCH_DTYPE records in the order given; None:
+        the last MatchDescriptors' list where it lies on the device, in device order) by RANSAC on
+        the device (PyramidContext.fit_homography) and return (the model record, whose `matrix` is
+        the 3 x 3 array or None, the inlier records sorted by `query`).  Nothing else is changed."""
+        self._ctx.set_ransac_input(matches)
+        self._ctx.fit_homography(hypotheses, seed, threshold, min_inliers)
+        return self._ctx.homography(), self._ctx.inliers()
 
     def output(self, file=None):
         """:89-104 — print scale 0 of each octave (space separated) and an `==` separator row."""

@@ -1,0 +1,187 @@
+"""The RANSAC homography at the C-ABI boundary, on a machine without a GPU: the eleven entry points are
+declared, exported and bound, reject null handles without touching outputs or the device, the
+homography record is 64 bytes in C, C++ and numpy alike, the drop-in classes' FitHomography compiles,
+and no export of the set takes a mutable context, orientation, describe or match object.  No compute
+call is made here."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from ransac_oracle import HOMOGRAPHY_DT
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(REPO, "sift-parallel-optimization_amd")
+INCLUDE = os.path.join(REPO, "include")
+
+FUNCTIONS = ("gdp_ransac_create", "gdp_ransac_destroy", "gdp_ransac_last_error", "gdp_ransac_set_input", "gdp_fit_homography",
+             "gdp_ransac_count", "gdp_download_homography", "gdp_download_hypotheses", "gdp_download_inliers", "gdp_device_inliers",
+             "gdp_ransac_layout")
+STRICT = ["-fsyntax-only", "-Wall", "-Wextra", "-Werror", "-I" + INCLUDE]
+
+
+def _header():
+    with open(os.path.join(INCLUDE, "gdp.h")) as f:
+        return f.read()
+
+
+def test_functions_declared_exported_and_bound(pkg):
+    from sift_parallel_optimization_amd._lib import SIGNATURES
+
+    declared = pkg.header_functions()
+    out = subprocess.run(["nm", "-D", "--defined-only", os.path.join(PKG, "lib", "libgdp.so")], capture_output=True,
+                         text=True, check=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
+    assert len(FUNCTIONS) == 11
+    for name in FUNCTIONS:
+        assert name in declared, name
+        assert name in exported, name
+        assert name in SIGNATURES, name
+    assert pkg.lib().gdp_abi_version() == 1
+    header = _header()
+    assert "#define GDP_ABI_VERSION 1\n" in header
+    assert "any 176 bytes are a valid record" in header  # the earlier steps' sentences stay
+    for word in ("0x7feb352d", "0x846ca68b", "0x9e3779b9", "adj[2][2] = M[0][0] * M[1][1] - M[0][1] * M[1][0]", "ldexp(G, -e)",
+                 "e <= (t * t) * (w * w)", "ties to the lowest h", "any 32 bytes are a valid record", "device order"):
+        assert word in header, word  # the rule is written into the header
+
+
+def test_no_export_of_the_set_takes_a_mutable_context_orient_describe_or_match():
+    """The design constraint of the earlier stages, one object further: the fit only reads the match
+    object, so the build that follows the whole chain is still the steady-state one."""
+    header = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    protos = {m.group(1): m.group(2) for m in re.finditer(r"\b(gdp_\w+)\s*\(([^;]*)\)\s*;", header)}
+    assert set(FUNCTIONS) <= set(protos)
+    with open(os.path.join(PKG, "csrc", "gdp.hip")) as f:
+        src = f.read()
+    for name in FUNCTIONS:
+        m = re.search(r"^[\w \*]+\b%s\(([^)]*)\)" % name, src, re.M)
+        assert m, name
+        for params in (protos[name], m.group(1)):
+            for handle in ("gdp_ctx", "gdp_orient", "gdp_describe", "gdp_match"):
+                assert not re.search(r"(?<!const )%s\s*\*" % handle, params), (name, params)
+    assert protos["gdp_ransac_create"].count("const gdp_match*") == 1
+
+
+def test_null_handles_are_argument_errors(pkg):
+    L = pkg.lib()
+    n, m = ctypes.c_size_t(7), ctypes.c_size_t(9)
+    u = [ctypes.c_uint32(5) for _ in range(3)]
+    recs, count, model, handle = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+    rec = np.zeros(1, pkg.MATCH_DTYPE)
+    out = np.zeros(1, pkg.HOMOGRAPHY_DTYPE)
+    assert L.gdp_ransac_create(ctypes.byref(handle), None, 0, 0) == 1 and handle.value is None
+    assert L.gdp_ransac_create(None, None, 16, 16) == 1
+    L.gdp_ransac_destroy(None)  # a no-op
+    assert L.gdp_ransac_set_input(None, ctypes.c_void_p(rec.ctypes.data), 1) == 1
+    assert L.gdp_fit_homography(None, 64, 0, 3.0, 4, None) == 1
+    assert L.gdp_ransac_count(None, ctypes.byref(n)) == 1
+    assert L.gdp_download_homography(None, ctypes.c_void_p(out.ctypes.data)) == 1
+    assert L.gdp_download_hypotheses(None, ctypes.c_void_p(out.ctypes.data), 1, ctypes.byref(n)) == 1
+    assert L.gdp_download_inliers(None, ctypes.c_void_p(rec.ctypes.data), 1, ctypes.byref(n), ctypes.byref(m)) == 1
+    assert L.gdp_device_inliers(None, ctypes.byref(recs), ctypes.byref(count), ctypes.byref(model)) == 1
+    assert L.gdp_ransac_layout(None, ctypes.byref(n), *[ctypes.byref(x) for x in u]) == 1
+    assert n.value == 7 and m.value == 9 and recs.value is None and count.value is None and model.value is None  # outputs untouched
+    assert [x.value for x in u] == [5, 5, 5] and not out.tobytes().strip(b"\0") and not rec.tobytes().strip(b"\0")
+    assert isinstance(L.gdp_ransac_last_error(None), bytes)
+
+
+def test_homography_dtype_matches_the_struct(pkg):
+    dt = pkg.HOMOGRAPHY_DTYPE
+    assert dt.itemsize == 64 and dt.names == ("h", "hypothesis", "inliers", "matches", "sample")
+    assert [dt.fields[n][1] for n in dt.names] == [0, 36, 40, 44, 48]
+    assert dt.fields["h"][0] == np.dtype((np.float32, (9,))) and dt.fields["sample"][0] == np.dtype((np.uint32, (4,)))
+    assert all(dt.fields[n][0] == np.uint32 for n in ("hypothesis", "inliers", "matches"))
+    assert all(HOMOGRAPHY_DT.fields[n] == dt.fields[n] for n in dt.names) and HOMOGRAPHY_DT.itemsize == 64
+
+
+def test_python_surface(pkg):
+    for name in ("set_ransac_capacity", "fit_homography", "homography", "hypotheses", "inliers", "inlier_count", "device_inliers",
+                 "set_ransac_input", "ransac_layout"):
+        assert callable(getattr(pkg.PyramidContext, name)), name
+    for cls in (pkg.GaussPyramid, pkg.GaussPyramid_a512omp, pkg.GaussPyramid_a512xp):
+        assert callable(cls.FitHomography)
+    from sift_parallel_optimization_amd._lib import check
+    import inspect
+
+    assert "ransac" in inspect.signature(check).parameters
+    rec = np.zeros((), pkg.HOMOGRAPHY_DTYPE)
+    rec["hypothesis"] = 0xFFFFFFFF
+    from sift_parallel_optimization_amd.gausspyramid import Homography
+
+    assert rec.view(Homography).matrix is None
+    rec["hypothesis"], rec["h"] = 3, np.arange(9)
+    assert rec.view(Homography).matrix.tolist() == [[0, 1, 2], [3, 4, 5], [6, 7, 8]]
+
+
+_LAYOUT = """
+#include <stddef.h>
+#include "gdp.h"
+%s(sizeof(gdp_homography) == 64, "four 16-byte stores per record");
+%s(offsetof(gdp_homography, h) == 0 && offsetof(gdp_homography, hypothesis) == 36 &&
+   offsetof(gdp_homography, inliers) == 40 && offsetof(gdp_homography, matches) == 44 &&
+   offsetof(gdp_homography, sample) == 48, "nine floats, three words, four indices");
+%s(sizeof(gdp_match_record) == 32 && offsetof(gdp_match_record, qx) == 16, "the coordinates are the record's second 16 bytes");
+int use(const gdp_match* src, const gdp_match_record* in, gdp_match_record* k, gdp_homography* h, size_t n) {
+    gdp_ransac* r = 0;
+    size_t stored = 0, found = 0, cap = 0;
+    const gdp_match_record* dev = 0;
+    const gdp_homography* model = 0;
+    const uint32_t* count = 0;
+    uint32_t most = 0, mt = 0, ht = 0;
+    int rc = gdp_ransac_create(&r, src, 0, 0) + gdp_ransac_set_input(r, in, n) + gdp_fit_homography(r, 1024, 0u, 3.0f, 4, 0) +
+             gdp_ransac_count(r, &found) + gdp_download_homography(r, h) + gdp_download_hypotheses(r, h, n, &stored) +
+             gdp_download_inliers(r, k, n, &stored, &found) + gdp_device_inliers(r, &dev, &count, &model) +
+             gdp_ransac_layout(r, &cap, &most, &mt, &ht);
+    rc += gdp_ransac_last_error(r) != 0;
+    gdp_ransac_destroy(r);
+    return rc;
+}
+"""
+
+
+@pytest.mark.parametrize("compiler,std,suffix,keyword", [("gcc", "-std=c11", ".c", "_Static_assert"),
+                                                          ("g++", "-std=c++14", ".cpp", "static_assert")])
+def test_record_is_64_bytes_in_c_and_cxx(tmp_path, compiler, std, suffix, keyword):
+    src = tmp_path / ("layout" + suffix)
+    src.write_text(_LAYOUT % ((keyword,) * 3))
+    subprocess.run([compiler, std] + STRICT + [str(src)], check=True)
+
+
+_DROPIN = """
+#include "%s"
+gdp_homography fit(%s& a, %s& b, std::vector<gdp_match_record>* inliers) {
+    return a.FitHomography(a.MatchDescriptors(b), inliers, 2048, 7u, 2.5f, 10);
+}
+bool defaults(%s& g) { return g.FitHomography(g.MatchDescriptors(g)).hypothesis != 0xffffffffu; }
+"""
+
+
+@pytest.mark.parametrize("header,cls", [("GaussDePyramid-HIP.h", "GaussPyramid_hip"),
+                                        ("GaussDePyramid-HIP-AVX512.h", "GaussPyramid_a512omp_hip"),
+                                        ("GaussDePyramid-HIP-AVX512.h", "GaussPyramid_a512xp_hip")])
+def test_dropin_fit_homography_compiles(tmp_path, header, cls):
+    src = tmp_path / "ransac.cpp"
+    src.write_text(_DROPIN % (header, cls, cls, cls))
+    subprocess.run(["g++", "-std=c++14"] + STRICT + [str(src)], check=True)
+
+
+def test_example_and_tool_are_wired():
+    with open(os.path.join(REPO, "examples", "Makefile")) as f:
+        mk = f.read()
+    assert mk.count("ransac_hip") >= 4  # in `all`, its rule (target + source) and `clean`
+    assert os.path.exists(os.path.join(REPO, "examples", "ransac_hip.cpp"))
+    assert os.path.exists(os.path.join(REPO, "tools", "ransac_bench.py"))
+    with open(os.path.join(PKG, "csrc", "Makefile")) as f:
+        mk = f.read()
+    assert "RANSAC := gdp_ransac.inc" in mk and "$(OUT)/libgdp.so asm exp: $(RANSAC)" in mk
+    with open(os.path.join(PKG, "csrc", "gdp.hip")) as f:
+        assert '#include "gdp_ransac.inc"' in f.read()
+    with open(os.path.join(REPO, ".gitignore")) as f:
+        assert "examples/ransac_hip\n" in f.read()
+    for doc, word in (("README.md", "gdp_fit_homography"), ("DESIGN.md", "5.10"), ("INTEGRATION.md", "FitHomography")):
+        with open(os.path.join(REPO, doc)) as f:
+            assert word in f.read(), (doc, word)
