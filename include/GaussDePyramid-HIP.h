@@ -128,6 +128,16 @@ public:
     // object lives for the call only.
     gdp_homography FitHomography(const std::vector<gdp_match_record>& matches, std::vector<gdp_match_record>* inliers = nullptr,
                                  uint32_t hypotheses = 1024, uint32_t seed = 0, float threshold = 3.0f, uint32_t min_inliers = 4);
+    // Extension: `other`'s input image resampled into this pyramid's frame (GDP_WARP_TRAIN_TO_QUERY), or
+    // this pyramid's into `other`'s (GDP_WARP_QUERY_TO_TRAIN, under the normalised adjugate), on the
+    // device (gdp_warp_image in gdp.h has the exact rule: `h` maps this pyramid's (x, y) to `other`'s,
+    // as FitHomography's h[] does; bilinear, ties to even, uncovered pixels store `fill`).  Returns the
+    // image row-major in *rows x *cols (either may be NULL) and, in *record when not NULL, the matrix
+    // used, `covered` and `sad`, the sum of absolute differences to the destination frame's image over
+    // the covered pixels.  Nothing of either pyramid or its lists is changed; the warp object lives for
+    // the call only.
+    std::vector<int32_t> WarpImage(GaussPyramid_hip& other, const float h[9], int direction = GDP_WARP_TRAIN_TO_QUERY,
+                                   int32_t fill = 0, gdp_warp_record* record = nullptr, int* rows = nullptr, int* cols = nullptr);
     ~GaussPyramid_hip();
     bool initialized;
     bool mirror_host;  // GaussPy two-way: upload before / download after every mutating call (default true)
@@ -536,6 +546,39 @@ inline gdp_homography GaussPyramid_hip::FitHomography(const std::vector<gdp_matc
     gdp_ransac_destroy(r);
     gdp_match_destroy(m);
     return model;
+}
+
+inline std::vector<int32_t> GaussPyramid_hip::WarpImage(GaussPyramid_hip& other, const float h[9], int direction, int32_t fill,
+                                                        gdp_warp_record* record, int* rows, int* cols) {
+    auto check = [](const char* last, int status) {
+        if (status != GDP_OK) {
+            std::fprintf(stderr, "GaussPyramid_hip::WarpImage failed: %s (%s)\n", gdp_status_string(status), last);
+            std::abort();
+        }
+    };
+    for (GaussPyramid_hip* g : {this, &other}) {
+        if (!g->orient_) check(gdp_orient_last_error(nullptr), gdp_orient_create(&g->orient_, g->ctx_, 0));
+        if (!g->describe_) check(gdp_describe_last_error(nullptr), gdp_describe_create(&g->describe_, g->ctx_, g->orient_, 0));
+    }
+    gdp_match* m = nullptr;  // the warp object reaches the two contexts through a fit and a match object; no list is read
+    check(gdp_match_last_error(nullptr), gdp_match_create(&m, describe_, other.describe_, 1, 1));
+    gdp_ransac* r = nullptr;
+    check(gdp_ransac_last_error(nullptr), gdp_ransac_create(&r, m, 1, 1));
+    gdp_warp* w = nullptr;
+    check(gdp_warp_last_error(nullptr), gdp_warp_create(&w, r));
+    check(gdp_warp_last_error(w), gdp_warp_set_model(w, h));
+    check(gdp_warp_last_error(w), gdp_warp_image(w, direction, 0, 0, fill, nullptr));
+    int height = 0, width = 0;
+    check(gdp_warp_last_error(w), gdp_device_warped(w, nullptr, nullptr, &height, &width, nullptr, nullptr));
+    std::vector<int32_t> out((size_t)height * (size_t)width);
+    check(gdp_warp_last_error(w), gdp_download_warped(w, out.data(), (size_t)width));
+    if (record) check(gdp_warp_last_error(w), gdp_download_warp_record(w, record));
+    if (rows) *rows = height;
+    if (cols) *cols = width;
+    gdp_warp_destroy(w);
+    gdp_ransac_destroy(r);
+    gdp_match_destroy(m);
+    return out;
 }
 
 inline void GaussPyramid_hip::output() {  // :89-104

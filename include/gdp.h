@@ -736,6 +736,103 @@ int gdp_device_inliers(const gdp_ransac* r, const gdp_match_record** records, co
 int gdp_ransac_layout(const gdp_ransac* r, size_t* capacity, uint32_t* max_hypotheses,
                       uint32_t* match_tile, uint32_t* hypothesis_tile);
 
+/* ---- extension: homography warp of an input image on the device ---------------------------------
+ * What the homography is for: one image resampled into the other's frame under the fitted model,
+ * stream-ordered behind the fit, with a measure of how well the two now agree (no reference
+ * counterpart, no parity claim).  The output is an image in the source context's input format, so a
+ * further context can bind it with gdp_set_input_device* and build a pyramid of the registered
+ * image.  It writes nothing of a context, an orientation, describe, match or ransac object: its state
+ * is an object of its own, gdp_warp, created from a const gdp_ransac.
+ *
+ * The rule.  Inputs: a model of nine float32 h[0..9), row-major, mapping query image coordinates
+ * (x, y) to train image coordinates as gdp_fit_homography produces it — x is the column index and y
+ * the row index of the octave-0 image, the convention of gdp_match_record; a SOURCE image (Hs x Ws,
+ * int32 or uint8); a DESTINATION FRAME image (Hd x Wd); an int32 `fill`; a `direction`:
+ *   GDP_WARP_TRAIN_TO_QUERY (0)  source = image train_image of the train context, destination frame =
+ *                                image query_image of the query context, M = h
+ *   GDP_WARP_QUERY_TO_TRAIN (1)  source = the query image, destination frame = the train image, M = the
+ *                                normalised adjugate of h (step 1)
+ *   1 matrix        (one thread, float64, every operation separately rounded, no division.)  When the
+ *                   model record says "none" (hypothesis == 0xffffffff) there is NO MODEL: m[] = 0,
+ *                   model = 0, every output pixel is `fill`, covered = 0, sad = 0.  Direction 0:
+ *                   m[k] = h[k] unchanged and model = 1, whatever the bytes are.  Direction 1: G = adj(h)
+ *                   with the nine expressions exactly as step 2 of the RANSAC rule writes them, h
+ *                   converted exactly to double;
+ *                     det = (h[0] * adj[0][0] + h[1] * adj[1][0]) + h[2] * adj[2][0];
+ *                   s = max |G[r][c]|.  If s is 0, infinite or NaN, or any entry is NaN, or det is 0 or
+ *                   NaN, there is no model (as above).  Otherwise s = mant * 2^e with mant in [0.5, 1)
+ *                   (frexp) and G <- ldexp(G, -e); G is negated when det < 0 (the pre-image of a point
+ *                   has positive w under h exactly when w' has det's sign, so after the negation the
+ *                   same w > 0 test serves both directions);  m[3r + c] = (float)G[r][c], round to
+ *                   nearest even, denormals kept
+ *   2 sample        (float32, every operation separately rounded, no contraction, denormals kept.)
+ *                   For output pixel (r, c), r < Hd, c < Wd:  x = (float)c,  y = (float)r,
+ *                     u = (m0 * x + m1 * y) + m2,  v = (m3 * x + m4 * y) + m5,  w = (m6 * x + m7 * y) + m8.
+ *                   If !(w > 0) the pixel is UNCOVERED.  sx = u / w, sy = v / w: two IEEE correctly
+ *                   rounded divisions.  The pixel is COVERED iff
+ *                     sx >= 0 && sy >= 0 && sx <= (float)(Ws - 1) && sy <= (float)(Hs - 1);  a NaN fails
+ *   3 interpolate   (covered pixels only.)  x0f = floorf(sx), y0f = floorf(sy);  x0 = (int)x0f,
+ *                   y0 = (int)y0f;  x1 = min(x0 + 1, Ws - 1),  y1 = min(y0 + 1, Hs - 1);
+ *                   fx = sx - x0f,  fy = sy - y0f;  pAB = (float)source[yA][xB] (int -> float, round to
+ *                   nearest even);
+ *                     top = p00 + fx * (p01 - p00),  bot = p10 + fx * (p11 - p10),
+ *                     val = top + fy * (bot - top),  q = rintf(val) (ties to even).
+ *                   int32 output: INT32_MAX when q >= 2147483648.0f, INT32_MIN when
+ *                   q < -2147483648.0f, else (int32_t)q.  uint8 output: clamped to 0..255.  The output
+ *                   format is the SOURCE context's input format
+ *   4 uncovered     pixels store `fill` (int32 output), or `fill` clamped to 0..255 (uint8 output)
+ *   5 statistics    `covered` is the number of covered pixels; `sad` is the sum over covered pixels of
+ *                   |out - dest[r][c]| as an exact uint64 integer sum, both read as integers whatever
+ *                   the two formats are.  Both are integer sums, so the result is independent of tiling
+ *                   and wave timing
+ *   6 addresses     no address is formed from anything but indices the coverage test has bounded: any
+ *                   nine floats and any pixel bytes are valid input
+ * Refusals: a row-band context is GDP_ERR_STATE; a destination frame of Hd * Wd >= 2^32 pixels, an
+ * image side above 16,777,216 (where (float)(Ws - 1) stops being exact), an image index out of range
+ * or a direction other than 0 / 1 are GDP_ERR_ARG, and nothing changes.  Out of scope: other
+ * interpolation kernels, anti-aliasing under minification, colour. */
+enum { GDP_WARP_TRAIN_TO_QUERY = 0, GDP_WARP_QUERY_TO_TRAIN = 1 };
+typedef struct gdp_warp_record {   /* 64 bytes */
+    float    m[9];                 /* the matrix step 2 used; all 0 without a model */
+    uint32_t model;                /* 1 / 0 */
+    uint32_t covered, pixels;      /* pixels = Hd * Wd of this launch */
+    uint64_t sad;
+    uint32_t direction, reserved;  /* reserved = 0 */
+} gdp_warp_record;
+typedef struct gdp_warp gdp_warp;
+/* A warp object reading one fit object (non-NULL) and, through its match object, the query and the
+ * train context: all are only read — the model record and the two input images (what
+ * gdp_device_input reports: the context's own buffer or a bound one) are looked up at every launch —
+ * and must outlive this object: destroy this one first.  The object owns one output buffer large
+ * enough for either direction in either format, the record and the caller's matrix.
+ * gdp_warp_last_error(w) describes w's last failure (w NULL: this thread's last failed create). */
+int gdp_warp_create(gdp_warp** out, const gdp_ransac* src);
+void gdp_warp_destroy(gdp_warp* w);
+const char* gdp_warp_last_error(const gdp_warp* w);
+/* Make h9[0..9) the model instead of the fit's model record (blocking).  The floats are not
+ * validated (point 6 of the rule); a caller's matrix is always a model in direction 0.  NULL goes
+ * back to the fit's model record. */
+int gdp_warp_set_model(gdp_warp* w, const float* h9);
+/* Warp: asynchronous and stream-ordered (NULL = the QUERY context's own stream).  The model record is
+ * read on the device, the host never reads it, so launching this right after gdp_fit_homography on
+ * the same stream is the normal use.  When the train context's input was written on another stream
+ * the caller orders it.  The output has the destination frame's size, the source context's input
+ * format and a row pitch of the width rounded up to 4 elements. */
+int gdp_warp_image(gdp_warp* w, int direction, int query_image, int train_image, int32_t fill, void* stream);
+/* The record of the last launch (blocking; waits for the query context's OWN stream; all 0 before any). */
+int gdp_download_warp_record(gdp_warp* w, gdp_warp_record* rec);
+/* The last launch's Hd x Wd output to host rows of `pitch_elements` elements of the output format
+ * (blocking); a pitch below Wd is GDP_ERR_ARG.  Nothing is copied before the first launch. */
+int gdp_download_warped(gdp_warp* w, void* host, size_t pitch_elements);
+/* Zero-copy view for device consumers (any output may be NULL): the output's first pixel, its pitch in
+ * elements — one gdp_set_input_device / gdp_set_input_device_u8 accept for a context of *height x
+ * *width in *format (GDP_INPUT_I32 / GDP_INPUT_U8) — and the record.  0 x 0 before the first launch. */
+int gdp_device_warped(const gdp_warp* w, const void** pixels, size_t* pitch, int* height, int* width,
+                      int* format, const gdp_warp_record** record);
+/* How the sweep cuts the destination frame (any output may be NULL): the rows and columns of a wave's
+ * tile and the consecutive columns one lane computes; a block is 2 x 2 such tiles. */
+int gdp_warp_layout(const gdp_warp* w, uint32_t* tile_rows, uint32_t* tile_cols, uint32_t* pixels_per_lane);
+
 /* ---- output --------------------------------------------------------------------------------
  * The blocking copies below are ordered after work on the context's OWN stream; if a build was
  * launched on another stream, synchronize that stream first. */

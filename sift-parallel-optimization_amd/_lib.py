@@ -167,6 +167,16 @@ SIGNATURES = {
     "gdp_device_inliers": (_c_int, [_p, _pp, _pp, _pp]),
     "gdp_ransac_layout": (_c_int, [_p, ctypes.POINTER(_c_size), ctypes.POINTER(_c_u32), ctypes.POINTER(_c_u32),
                                    ctypes.POINTER(_c_u32)]),
+    "gdp_warp_create": (_c_int, [_pp, _p]),
+    "gdp_warp_destroy": (None, [_p]),
+    "gdp_warp_last_error": (ctypes.c_char_p, [_p]),
+    "gdp_warp_set_model": (_c_int, [_p, _p]),
+    "gdp_warp_image": (_c_int, [_p, _c_int, _c_int, _c_int, ctypes.c_int32, _p]),
+    "gdp_download_warp_record": (_c_int, [_p, _p]),
+    "gdp_download_warped": (_c_int, [_p, _p, _c_size]),
+    "gdp_device_warped": (_c_int, [_p, _pp, ctypes.POINTER(_c_size), ctypes.POINTER(_c_int), ctypes.POINTER(_c_int),
+                                   ctypes.POINTER(_c_int), _pp]),
+    "gdp_warp_layout": (_c_int, [_p, ctypes.POINTER(_c_u32), ctypes.POINTER(_c_u32), ctypes.POINTER(_c_u32)]),
     "gdp_checksum": (_c_int, [_p, _c_int, ctypes.POINTER(ctypes.c_uint64)]),
     "gdp_get_taps": (_c_int, [_p, _c_int, _c_int, _c_int, _p]),
     "gdp_set_window_centre": (_c_int, [_p, _c_int]),
@@ -229,13 +239,16 @@ def build_variants():
     return list(ids)
 
 
-def check(status, ctx=None, orient=False, describe=False, match=False, ransac=False):
+def check(status, ctx=None, orient=False, describe=False, match=False, ransac=False, warp=False):
     """Raise GdpError for a non-zero status; `ctx` is the context whose gdp_last_error describes it
     (orient=True: a gdp_orient object, or None for a failed gdp_orient_create; describe=True,
-    match=True and ransac=True: the same for a gdp_describe, a gdp_match and a gdp_ransac object)."""
+    match=True, ransac=True and warp=True: the same for a gdp_describe, a gdp_match, a gdp_ransac and
+    a gdp_warp object)."""
     if status != GDP_OK:
         L = lib()
-        if ransac:
+        if warp:
+            msg = L.gdp_warp_last_error(ctx)
+        elif ransac:
             msg = L.gdp_ransac_last_error(ctx)
         elif match:
             msg = L.gdp_match_last_error(ctx)

@@ -60,6 +60,7 @@ namespace {
 #include "gdp_describe.inc"
 #include "gdp_match.inc"
 #include "gdp_ransac.inc"
+#include "gdp_warp.inc"
 #include "gdp_util.inc"
 #include "gdp_track.inc"
 
@@ -294,6 +295,22 @@ struct gdp_ransac : ErrorState {
     uint32_t* d_count = nullptr;           // one counter
     gdp_match_record* d_in = nullptr;      // the caller's list, allocated on first use
     uint32_t* d_in_count = nullptr;        // its length; kRaNoList = the match object's list
+};
+
+// gdp_warp_create: the warp's state.  It reads one gdp_ransac object (its model record) and, through
+// it, the two contexts' input images, all looked up at every launch and never written; it owns
+// everything it writes.
+struct gdp_warp : ErrorState {
+    const gdp_ransac* src = nullptr;
+    int device = 0;                        // the fit object's device
+    void* d_out = nullptr;                 // the warped image: room for either direction in either format
+    size_t out_elements = 0;               // its size in int32 elements
+    gdp_warp_record* d_rec = nullptr;      // the record (all 0 before the first launch)
+    float* d_h = nullptr;                  // the caller's nine floats
+    bool own_model = false;                // launches read d_h, not the fit's model record
+    int height = 0, width = 0;             // the last launch's destination frame (0 x 0 before any)
+    int format = GDP_INPUT_I32;            // its output format: the source context's input format then
+    size_t pitch = 0;                      // its row pitch in elements: the width rounded up to 4
 };
 
 namespace {
@@ -794,6 +811,7 @@ const gdp_ctx* ctx_of(const gdp_orient* w) { return w->ctx; }
 const gdp_ctx* ctx_of(const gdp_describe* w) { return w->ctx; }
 const gdp_ctx* ctx_of(const gdp_match* m) { return m->side[0]->ctx; }
 const gdp_ctx* ctx_of(const gdp_ransac* r) { return ctx_of(r->src); }
+const gdp_ctx* ctx_of(const gdp_warp* w) { return ctx_of(w->src); }
 
 // d_in_count of a slot that reads its producer's list, not the caller's
 constexpr uint32_t kNoList = 0xffffffffu;
@@ -3658,6 +3676,170 @@ int gdp_device_inliers(const gdp_ransac* r, const gdp_match_record** records, co
     if (records) *records = r->d_out;
     if (count) *count = r->d_count;
     if (model) *model = r->d_model;
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+// ---- extension: homography warp of an input image (gdp_warp.inc) -----------------------------------
+// No export below takes a mutable context, orientation, describe, match or ransac object: the state is
+// the gdp_warp object's; the model record and the two contexts' input images are read.
+
+static_assert(sizeof(gdp_warp_record) == 64 && offsetof(gdp_warp_record, sad) == 48, "the layout gdp.h documents");
+
+// the two contexts of a warp: 0 query, 1 train
+static const gdp_ctx* warp_side(const gdp_warp* w, int side) { return w->src->src->side[side]->ctx; }
+
+void gdp_warp_destroy(gdp_warp* w) {
+    if (!w) return;
+    (void)hipSetDevice(w->device);
+    (void)hipDeviceSynchronize();  // a launch on any stream may still read or write the buffers
+    if (w->d_out) (void)hipFree(w->d_out);
+    if (w->d_rec) (void)hipFree(w->d_rec);
+    if (w->d_h) (void)hipFree(w->d_h);
+    delete w;
+}
+
+int gdp_warp_create(gdp_warp** out, const gdp_ransac* src) try {
+    if (!out || !src) return GDP_ERR_ARG;
+    hipError_t e = hipSetDevice(src->device);
+    if (e != hipSuccess) return create_fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    gdp_warp* w = new gdp_warp;
+    w->src = src;
+    w->device = src->device;
+    // either context's frame, rows padded to 4 elements, in the wider format.  No list and no counters:
+    // finish_create does not fit, create_failed does
+    for (int side = 0; side < 2; ++side) {
+        const Geom& g = warp_side(w, side)->geom;
+        w->out_elements = std::max(w->out_elements, (size_t)g.H * (size_t)round_up(g.W, kWpLanePixels));
+    }
+    e = hipMalloc(&w->d_out, std::max<size_t>(16, w->out_elements * sizeof(int32_t)));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_rec), sizeof(gdp_warp_record));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_h), 9 * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(w->d_rec, 0, sizeof(gdp_warp_record));
+    if (e == hipSuccess) e = hipMemset(w->d_h, 0, 9 * sizeof(float));
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // a context's non-blocking stream does not wait for the fills
+    if (e != hipSuccess)
+        return create_failed(w, gdp_warp_destroy, "gdp_warp_create (" + std::to_string(w->out_elements) + " pixels): ", e);
+    *out = w;
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+const char* gdp_warp_last_error(const gdp_warp* w) { return w ? w->err.c_str() : g_create_error.c_str(); }
+
+int gdp_warp_layout(const gdp_warp* w, uint32_t* tile_rows, uint32_t* tile_cols, uint32_t* pixels_per_lane) try {
+    if (!w) return GDP_ERR_ARG;
+    if (tile_rows) *tile_rows = kWpTileRows;
+    if (tile_cols) *tile_cols = kWpTileCols;
+    if (pixels_per_lane) *pixels_per_lane = kWpLanePixels;
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+int gdp_warp_set_model(gdp_warp* w, const float* h9) try {
+    if (!w) return GDP_ERR_ARG;
+    if (!h9) {
+        w->own_model = false;
+        return GDP_OK;
+    }
+    const gdp_ctx* c = ctx_of(w);
+    GDP_HIP(w, hipSetDevice(c->device));
+    GDP_SETTLE(w, "gdp_warp_set_model", [&](auto&& f) { f(h9, 9 * sizeof(float)); });
+    // the nine floats are data: the kernels form no address from them, so nothing is validated
+    GDP_HIP(w, hipMemcpyAsync(w->d_h, track_dma_ptr(h9), 9 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    GDP_HIP(w, hipStreamSynchronize(c->stream));
+    w->own_model = true;
+    return GDP_OK;
+} GDP_ABI_CATCH(w)
+
+int gdp_warp_image(gdp_warp* w, int direction, int query_image, int train_image, int32_t fill, void* stream) try {
+    if (!w) return GDP_ERR_ARG;
+    const gdp_ctx *q = warp_side(w, 0), *t = warp_side(w, 1);
+    if (direction != GDP_WARP_TRAIN_TO_QUERY && direction != GDP_WARP_QUERY_TO_TRAIN)
+        return w->status(GDP_ERR_ARG, "gdp_warp_image: direction %d is neither GDP_WARP_TRAIN_TO_QUERY nor GDP_WARP_QUERY_TO_TRAIN",
+                         direction);
+    if (query_image < 0 || query_image >= q->geom.batch || train_image < 0 || train_image >= t->geom.batch)
+        return w->status(GDP_ERR_ARG, "gdp_warp_image: image %d / %d out of range (batch %d / %d)", query_image, train_image,
+                         q->geom.batch, t->geom.batch);
+    for (const gdp_ctx* c : {q, t}) {
+        const std::string band = row_band_error(c->geom, "gdp_warp_image", "image", "warp");
+        if (!band.empty()) return w->status(GDP_ERR_STATE, "%s", band.c_str());
+    }
+    const bool to_query = direction == GDP_WARP_TRAIN_TO_QUERY;
+    const gdp_ctx *s = to_query ? t : q, *d = to_query ? q : t;
+    const int si = to_query ? train_image : query_image, di = to_query ? query_image : train_image;
+    const Geom &gs = s->geom, &gd = d->geom;
+    if ((unsigned long long)gd.H * (unsigned long long)gd.W >= (1ull << 32))
+        return w->status(GDP_ERR_ARG, "gdp_warp_image: a destination frame of 2^32 pixels or more");
+    if (gs.H < 1 || gs.W < 1 || gd.H < 1 || gd.W < 1 || gs.H > kWpMaxDim || gs.W > kWpMaxDim || gd.H > kWpMaxDim || gd.W > kWpMaxDim)
+        return w->status(GDP_ERR_ARG, "gdp_warp_image: an image side outside 1..16,777,216 (the pixel coordinates are exact floats)");
+    const bool u8 = gs.in_fmt == GDP_INPUT_U8;
+    WarpGeom g{};
+    g.src = static_cast<const char*>(s->d_in) + (size_t)si * (size_t)gs.in_img_stride * in_elem_size(s);
+    g.dst = static_cast<const char*>(d->d_in) + (size_t)di * (size_t)gd.in_img_stride * in_elem_size(d);
+    g.out = w->d_out;
+    g.src_pitch = (size_t)gs.in_pitch;
+    g.dst_pitch = (size_t)gd.in_pitch;
+    g.out_pitch = (size_t)round_up(gd.W, kWpLanePixels);
+    g.Hs = gs.H, g.Ws = gs.W, g.Hd = gd.H, g.Wd = gd.W;
+    g.xmax = (float)(gs.W - 1);
+    g.ymax = (float)(gs.H - 1);
+    g.fill = fill;
+    g.blocks_x = (unsigned)((gd.W + kWpBlockCols - 1) / kWpBlockCols);
+    const uintptr_t align = gd.in_fmt == GDP_INPUT_U8 ? 3 : 15;  // one uchar4 / int4 load per lane
+    g.dst_vec = (reinterpret_cast<uintptr_t>(g.dst) & align) == 0 && g.dst_pitch % kWpLanePixels == 0 ? 1 : 0;
+    const unsigned long long blocks = (unsigned long long)g.blocks_x * (unsigned)((gd.H + kWpBlockRows - 1) / kWpBlockRows);
+    if (blocks >= (1ull << 31)) return w->status(GDP_ERR_ARG, "gdp_warp_image: too many tiles for one launch");
+    g.tiles = (unsigned)blocks;
+    // at most eight blocks per CU, each sweeping its tiles: the two counters take one pair of atomics per BLOCK, all
+    // on one cache line, and one pair per tile was what a 4096^2 frame's time consisted of
+    const unsigned grid = (unsigned)std::min<unsigned long long>(blocks, (unsigned long long)q->blocks_max);
+    GDP_HIP(w, hipSetDevice(w->device));
+    hipStream_t st = q->pick(stream);
+    w->height = gd.H, w->width = gd.W, w->format = gs.in_fmt, w->pitch = g.out_pitch;
+    hipLaunchKernelGGL(k_warp_prepare, dim3(1), dim3(64), 0, st, reinterpret_cast<const uint32_t*>(w->src->d_model),
+                       w->own_model ? w->d_h : static_cast<const float*>(nullptr), direction, (uint32_t)((size_t)gd.H * (size_t)gd.W),
+                       w->d_rec);
+    auto k = u8 ? (gd.in_fmt == GDP_INPUT_U8 ? k_warp<true, true> : k_warp<true, false>)
+                : (gd.in_fmt == GDP_INPUT_U8 ? k_warp<false, true> : k_warp<false, false>);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, g, reinterpret_cast<const uint32_t*>(w->d_rec), &w->d_rec->covered,
+                       reinterpret_cast<unsigned long long*>(&w->d_rec->sad));
+    GDP_HIP(w, hipGetLastError());
+    return GDP_OK;
+} GDP_ABI_CATCH(w)
+
+int gdp_download_warp_record(gdp_warp* w, gdp_warp_record* rec) try {
+    if (!w || !rec) return w ? w->status(GDP_ERR_ARG, "gdp_download_warp_record: bad argument") : GDP_ERR_ARG;
+    const gdp_ctx* c = ctx_of(w);
+    GDP_HIP(w, hipSetDevice(c->device));
+    GDP_SETTLE(w, "gdp_download_warp_record", [&](auto&& f) { f(rec, sizeof *rec); });
+    GDP_HIP(w, hipMemcpyAsync(track_dma_ptr(rec), w->d_rec, sizeof *rec, hipMemcpyDeviceToHost, c->stream));
+    GDP_HIP(w, hipStreamSynchronize(c->stream));
+    return GDP_OK;
+} GDP_ABI_CATCH(w)
+
+int gdp_download_warped(gdp_warp* w, void* host, size_t pitch_elements) try {
+    if (!w) return GDP_ERR_ARG;
+    if (w->height == 0) return GDP_OK;  // no launch yet: nothing to copy
+    if (!host || pitch_elements < (size_t)w->width)
+        return w->status(GDP_ERR_ARG, "gdp_download_warped: a NULL buffer or a pitch below the width %d", w->width);
+    const gdp_ctx* c = ctx_of(w);
+    const size_t esz = w->format == GDP_INPUT_U8 ? 1 : 4;
+    GDP_HIP(w, hipSetDevice(c->device));
+    GDP_SETTLE(w, "gdp_download_warped",
+               [&](auto&& f) { f(host, ((size_t)(w->height - 1) * pitch_elements + (size_t)w->width) * esz); });
+    GDP_HIP(w, hipMemcpy2DAsync(track_dma_ptr(host), pitch_elements * esz, w->d_out, w->pitch * esz, (size_t)w->width * esz,
+                                (size_t)w->height, hipMemcpyDeviceToHost, c->stream));
+    GDP_HIP(w, hipStreamSynchronize(c->stream));
+    return GDP_OK;
+} GDP_ABI_CATCH(w)
+
+int gdp_device_warped(const gdp_warp* w, const void** pixels, size_t* pitch, int* height, int* width, int* format,
+                      const gdp_warp_record** record) try {
+    if (!w) return GDP_ERR_ARG;
+    if (pixels) *pixels = w->d_out;
+    if (pitch) *pitch = w->pitch;
+    if (height) *height = w->height;
+    if (width) *width = w->width;
+    if (format) *format = w->format;
+    if (record) *record = w->d_rec;
     return GDP_OK;
 } GDP_ABI_CATCH(nullptr)
 

@@ -93,6 +93,14 @@ HOMOGRAPHY_DTYPE = np.dtype({"names": ["h", "hypothesis", "inliers", "matches", 
                              "offsets": [0, 36, 40, 44, 48], "itemsize": 64})
 
 
+# struct gdp_warp_record (include/gdp.h): 64 bytes
+WARP_DTYPE = np.dtype({"names": ["m", "model", "covered", "pixels", "sad", "direction", "reserved"],
+                       "formats": [(np.float32, (9,)), np.uint32, np.uint32, np.uint32, np.uint64, np.uint32, np.uint32],
+                       "offsets": [0, 36, 40, 44, 48, 56, 60], "itemsize": 64})
+
+WARP_DIRECTIONS = {"train_to_query": 0, "query_to_train": 1}  # GDP_WARP_TRAIN_TO_QUERY, GDP_WARP_QUERY_TO_TRAIN
+
+
 class Homography(np.ndarray):
     """One HOMOGRAPHY_DTYPE record (0-d) with `matrix`: its 3 x 3 float32 array, row-major as scored,
     or None when the record holds no model."""
@@ -836,6 +844,7 @@ class PyramidContext:
         return r
 
     def _drop_ransac(self):
+        self._drop_warp()  # it reads the fit object: it goes first
         r = getattr(self, "_ransac", None)
         if r is not None and r.value:
             lib().gdp_ransac_destroy(r)
@@ -926,6 +935,84 @@ class PyramidContext:
         most, mt, ht = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
         check(lib().gdp_ransac_layout(r, ctypes.byref(cap), ctypes.byref(most), ctypes.byref(mt), ctypes.byref(ht)), r, ransac=True)
         return cap.value, most.value, mt.value, ht.value
+
+    # ------------------------------------------------------------------ homography warp (extension)
+    def _warp_handle(self):
+        """The gdp_warp object that reads this context's current fit object, created on first use and
+        again whenever the fit object is (it is dropped before the fit object it reads)."""
+        r = self._ransac_handle()
+        w = getattr(self, "_warp", None)
+        if w is not None and w.value and self._warp_of == r.value:
+            return w
+        self._drop_warp()
+        w = ctypes.c_void_p()
+        check(lib().gdp_warp_create(ctypes.byref(w), r), None, warp=True)
+        self._warp, self._warp_of = w, r.value
+        return w
+
+    def _drop_warp(self):
+        w = getattr(self, "_warp", None)
+        if w is not None and w.value:
+            lib().gdp_warp_destroy(w)
+            self._warp = ctypes.c_void_p()
+
+    def warp_image(self, direction="train_to_query", query_image=0, train_image=0, fill=0, stream=None):
+        """Resample one input image into the other's frame under the last fit's model record (or
+        set_warp_model's matrix) on the device (gdp_warp_image: 'train_to_query' brings image
+        `train_image` of the matched train context into image `query_image`'s frame of this context,
+        'query_to_train' the other way round under the normalised adjugate; bilinear, ties to even,
+        uncovered pixels store `fill`); asynchronous on `stream`, no host read of the model."""
+        w = self._warp_handle()
+        code = WARP_DIRECTIONS.get(direction, direction)
+        check(lib().gdp_warp_image(w, int(code), int(query_image), int(train_image), int(fill), _stream_handle(stream)), w, warp=True)
+
+    def set_warp_model(self, h):
+        """Make the nine floats of `h` (3 x 3 or flat, row-major, query -> train) the model a warp
+        reads instead of the fit's model record (blocking; the floats are not validated); None goes
+        back to the fit's."""
+        w = self._warp_handle()
+        if h is None:
+            check(lib().gdp_warp_set_model(w, None), w, warp=True)
+            return
+        h = np.ascontiguousarray(h, dtype=np.float32).reshape(-1)
+        if h.size != 9:
+            raise ValueError("a warp model is nine floats")
+        check(lib().gdp_warp_set_model(w, _ptr(h)), w, warp=True)
+
+    def warp_record(self):
+        """The last warp's WARP_DTYPE record (blocking; all 0 before any)."""
+        w = self._warp_handle()
+        out = np.zeros(1, WARP_DTYPE)
+        check(lib().gdp_download_warp_record(w, _ptr(out)), w, warp=True)
+        return out[0]
+
+    def device_warped(self):
+        """(device address of the warped image, pitch in elements, height, width, 'i32' or 'u8', device
+        address of the record): what a context of that size and format binds with bind_device_input."""
+        w = self._warp_handle()
+        pix, rec, pitch = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        h, wd, fmt = _i(), _i(), _i()
+        check(lib().gdp_device_warped(w, ctypes.byref(pix), ctypes.byref(pitch), ctypes.byref(h), ctypes.byref(wd), ctypes.byref(fmt),
+                                      ctypes.byref(rec)), w, warp=True)
+        return pix.value, pitch.value, h.value, wd.value, "u8" if fmt.value == 1 else "i32", rec.value
+
+    def warped(self):
+        """The last warp's output as a numpy array of the destination frame's shape in the output
+        format, int32 or uint8 (blocking; 0 x 0 before any)."""
+        w = self._warp_handle()
+        _, _, h, wd, fmt, _ = self.device_warped()
+        out = np.zeros((h, wd), np.uint8 if fmt == "u8" else np.int32)
+        if out.size:
+            check(lib().gdp_download_warped(w, _ptr(out), wd), w, warp=True)
+        return out
+
+    def warp_layout(self):
+        """(rows, columns of a wave's tile of the destination frame, consecutive columns per lane)
+        (gdp_warp_layout)."""
+        w = self._warp_handle()
+        tr, tc, ppl = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        check(lib().gdp_warp_layout(w, ctypes.byref(tr), ctypes.byref(tc), ctypes.byref(ppl)), w, warp=True)
+        return tr.value, tc.value, ppl.value
 
     def device_level_ptr(self, b, o, s):
         """Device address of level (o, s) of image b.  Read-only: after writing through it, call
@@ -1105,6 +1192,19 @@ class GaussPyramid:
         self._ctx.set_ransac_input(matches)
         self._ctx.fit_homography(hypotheses, seed, threshold, min_inliers)
         return self._ctx.homography(), self._ctx.inliers()
+
+    def WarpImage(self, other=None, model=None, direction="train_to_query", fill=0):
+        """Extension: resample `other`'s input image (the train side; None: the train side of the
+        last MatchDescriptors, or this pyramid) into this pyramid's frame — or, with
+        direction='query_to_train', this pyramid's into `other`'s — under `model` (nine floats mapping
+        this pyramid's (x, y) to `other`'s; None: the last FitHomography's model record, read on the
+        device) on the device (PyramidContext.warp_image).  Returns (the warped image, int32, and the
+        WARP_DTYPE record with `covered` and `sad`).  Neither pyramid nor any list is changed."""
+        if other is not None:
+            self._ctx._match_handle(other._ctx)
+        self._ctx.set_warp_model(model)
+        self._ctx.warp_image(direction, 0, 0, fill)
+        return self._ctx.warped(), self._ctx.warp_record()
 
     def output(self, file=None):
         """:89-104 — print scale 0 of each octave (space separated) and an `==` separator row."""
