@@ -1083,7 +1083,7 @@ enum {
                                    clears GDP_TUNE_ZEROS_CLEAN, or after any other kind of build,
                                    stores everything and writes the map; the saving starts with the
                                    second.  A build that skips by the map runs k_keep with 4 rows
-                                   per wave at every size (it barely stores; read-only
+                                   per wave above 4 Mpix (it barely stores; read-only
                                    GDP_TUNE_KEEP_SIGNS_KERNEL), unless GDP_TUNE_KEEP_KERNEL was set
                                    by the caller; the build that writes the map makes every store
                                    and keeps GDP_TUNE_KEEP_KERNEL's shape.  uint8 input stores as before.  The same bits
@@ -1095,12 +1095,24 @@ enum {
                                    build and by a switch of GDP_TUNE_KEEP_SIGNS) */
     GDP_TUNE_KEEP_SIGNS_KERNEL = 26, /* read-only: the k_keep shape (a GDP_TUNE_KEEP_KERNEL value) of a
                                    build that skips by the sign map; 0 while GDP_TUNE_KEEP_KERNEL is 0 */
+    GDP_TUNE_KEEP_SUPPORT = 27, /* 1 (default): k_keep runs the 4-pixel groups of the tiles that meet
+                                   the windows' support — the only ones that are computed, not just
+                                   given their sign — as work units of their own, 256 groups each,
+                                   dispatched ahead of the 16 x 256 tiles, instead of in several
+                                   serial rounds at the end of those tiles' blocks.  0 = in the
+                                   tiles' blocks.  Every word is stored by the same code from the
+                                   same pixel: the same bits either way, and a switch leaves
+                                   GDP_TUNE_ZEROS_CLEAN and GDP_TUNE_SIGNS_KNOWN as they are.  A
+                                   launch-time flag: no drain */
+    GDP_TUNE_KEEP_SUPPORT_UNITS = 28, /* read-only: the number of those units in the context's next
+                                   k_keep launch; 0 with GDP_TUNE_KEEP_SUPPORT = 0 or where k_keep
+                                   does not take the context (GDP_TUNE_KEEP_KERNEL) */
     GDP_TUNE_KEEP_KERNEL = 23  /* the kernel of a gdp_build that skips those stores (the steady
                                    state): 0 = the build kernel's own keep path; 1, 2 = the
                                    steady-state kernel k_keep — one pass over the input on
                                    16 x 256 tiles, level S+2 of every fused octave stored from the
                                    registers that hold the octave-0 pixels — with 4 or 2 rows per
-                                   wave (default by pixels per launch: 0 under 8 Mpix, 2 up to 64 Mpix,
+                                   wave (default by pixels per launch: 0 under 1.5 Mpix, 2 up to 64 Mpix,
                                    1 above).  Taken when the width is a multiple of 4 and the input
                                    allows one vector load per 4 pixels; any other context runs 0.
                                    The same bits either way.  A launch-time flag: no drain */

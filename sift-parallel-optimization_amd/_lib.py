@@ -36,6 +36,8 @@ GDP_TUNE_KEEP_KERNEL = 23
 GDP_TUNE_KEEP_SIGNS = 24
 GDP_TUNE_SIGNS_KNOWN = 25
 GDP_TUNE_KEEP_SIGNS_KERNEL = 26
+GDP_TUNE_KEEP_SUPPORT = 27
+GDP_TUNE_KEEP_SUPPORT_UNITS = 28
 
 
 class GdpError(RuntimeError):

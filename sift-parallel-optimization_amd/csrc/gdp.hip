@@ -186,7 +186,9 @@ struct gdp_ctx : ErrorState {
     int keep_kernel_signs = 1;    // GDP_TUNE_KEEP_SIGNS_KERNEL: the k_keep shape (kKeepKernels id) of a launch that skips by
                                   // the map (kSignsUse), where keep_kernel >= 1 takes k_keep at all: its own default by
                                   // measurement; GDP_TUNE_KEEP_KERNEL sets both
-    long long img_floats = 0;     // one image's dense extent (pyr_stride may be larger: GDP_IMAGE_STRIDE_MB)
+    int keep_support = 1;         // GDP_TUNE_KEEP_SUPPORT: 1 = k_keep runs the groups inside the windows' support as units
+                                  // of their own (Geom::kp_sup_units), 0 = in their tiles' blocks; a kernel argument
+    long long img_floats = 0;    // one image's dense extent (pyr_stride may be larger: GDP_IMAGE_STRIDE_MB)
     // GDP_SPREAD_VMM: the pyramid as one reserved address range with separately created physical
     // chunks mapped into it (alloc_spread); each entry: handle, byte offset, bytes
     struct VmmChunk {
@@ -396,6 +398,13 @@ inline void pyramid_written(gdp_ctx* c) {
 #define GDP_READS_PYRAMID(ctx) ((void)(ctx))
 #define GDP_BUILDS_PYRAMID(ctx) ((void)(ctx))  // gdp_build and the build timers: launch_build keeps the flag itself
 
+// GDP_TUNE_KEEP_SUPPORT_UNITS: the support units of the context's next k_keep launch — none with
+// GDP_TUNE_KEEP_SUPPORT = 0 or where k_keep does not take the context (launch_build's test).
+unsigned keep_support_units(const gdp_ctx* c) {
+    const Geom& g = c->geom;
+    return (c->keep_support && c->keep_kernel > 0 && g.W % 4 == 0 && g.vec_in) ? g.kp_sup_units : 0u;
+}
+
 int launch_build(gdp_ctx* c, hipStream_t st, bool subset = false) {
     const Geom& g = c->geom;
     const long long units = (long long)g.tiles_total + g.tail_units;
@@ -414,7 +423,11 @@ int launch_build(gdp_ctx* c, hipStream_t st, bool subset = false) {
         // The steady-state build's own kernel (gdp_keep.inc): whole 4-pixel groups and aligned vector
         // loads everywhere; any other context keeps k_build's keep path below.  Its units are the
         // Geom's kp_* fields, whatever variant is selected; a launch-time choice like `keep` itself.
-        const long long kunits = (long long)g.kp_tiles_total + g.kp_tail_units;
+        // GDP_TUNE_KEEP_SUPPORT: the groups inside the windows' support as units of their own, ahead of the tiles
+        const int support = keep_support_units(c) > 0 ? 1 : 0;
+        const long long kunits = (long long)keep_support_units(c) + g.kp_tiles_total + g.kp_tail_units;
+        // one unit per block of this kernel's own unit space (`cap` above counts the selected build variant's units)
+        const long long kcap = c->grid_override > 0 ? c->grid_override : (c->persistent ? c->blocks_max : kunits);
         // The sign map (GDP_TUNE_KEEP_SIGNS): int32 input only (a uint8 launch stores +0 without
         // reading and leaves the map stale).  The first launch after anything that invalidated the
         // map stores everything and writes it; the ones after skip the rows that owe nothing.
@@ -423,8 +436,8 @@ int launch_build(gdp_ctx* c, hipStream_t st, bool subset = false) {
         // whatever the rows per wave) keeps GDP_TUNE_KEEP_KERNEL's; only the skipping launch takes its own default.
         const KeepKernel& kk = kKeepKernels[(mode == kSignsUse ? c->keep_kernel_signs : c->keep_kernel) - 1];
         // (kSignsOff launches the instantiation without the map's code: the kernel as it was before the map)
-        hipLaunchKernelGGL(kk.k[mode != kSignsOff][c->nontemporal ? 1 : 0], dim3((unsigned)std::min<long long>(kunits, cap)),
-                           dim3(kk.block), 0, st, c->d_geom, c->d_in, c->d_out, c->d_taps, c->d_signs, mode);
+        hipLaunchKernelGGL(kk.k[mode != kSignsOff][c->nontemporal ? 1 : 0], dim3((unsigned)std::min<long long>(kunits, kcap)),
+                           dim3(kk.block), 0, st, c->d_geom, c->d_in, c->d_out, c->d_taps, support, c->d_signs, mode);
         GDP_HIP(c, hipGetLastError());
         c->zeros_clean = true;  // keep != 0: a full build into the context's own pyramid
         c->signs_known = mode != kSignsOff;
@@ -541,6 +554,58 @@ void fill_host_taps(gdp_ctx* c, int mode) {
 // of every octave), and only copied in and out of the Geom when the knob changes.  OctGeom::sp_*
 // always hold them: a build on a clean pyramid (gdp_ctx::zeros_clean) skips the DoG stores outside
 // them whatever the knob says.
+// k_keep's support units (gdp_keep.inc, GDP_TUNE_KEEP_SUPPORT): per fused octave the rectangle of
+// tiles whose footprint meets OctGeom::sp_* and its footprint in 4-pixel groups.  The tile test is
+// the one the kernel made per tile before it read these intervals — an interval test in tile rows
+// times one in tile columns (r_lo, r_hi and c_lo, c_hi never decrease with the tile index) — so the
+// first and last hit of each direction bound the set exactly.  Too many groups for a 31-bit unit
+// count (never on a real support, which is a few dozen rows and columns per octave): no units, the
+// launch keeps the groups in the tiles' blocks.
+void keep_support_geom(Geom& g) {
+    const int tiles_r = (g.in_rows + kTileRows - 1) / kTileRows;
+    long long per = 0;
+    g.kp_sup_begin[0] = 0;
+    for (int o = 0; o < kFused; ++o) {
+        int tr0 = 0, tr1 = 0, tc0 = 0, tc1 = 0;
+        if (o < g.kp_F) {
+            const OctGeom& og = g.oct[o];
+            bool any = false;
+            for (int tr = 0; tr < tiles_r; ++tr) {
+                const int r_lo = og.row0 + ((tr * kTileRows) >> o), r_hi = r_lo + (kTileRows >> o);
+                if (r_lo < og.sp_r1 && r_hi > og.sp_r0) {
+                    if (!any) tr0 = tr;
+                    tr1 = tr + 1;
+                    any = true;
+                }
+            }
+            any = false;
+            for (int tc = 0; tc < g.kp_tiles_c; ++tc) {
+                const int c_lo = (tc * kTileCols) >> o, c_hi = std::min(c_lo + (kTileCols >> o), og.cols);
+                if (c_lo < og.sp_c1 && c_hi > og.sp_c0) {
+                    if (!any) tc0 = tc;
+                    tc1 = tc + 1;
+                    any = true;
+                }
+            }
+            if (tr0 == tr1 || tc0 == tc1) tr0 = tr1 = tc0 = tc1 = 0;
+        }
+        g.kp_sl_tr0[o] = tr0, g.kp_sl_tr1[o] = tr1, g.kp_sl_tc0[o] = tc0, g.kp_sl_tc1[o] = tc1;
+        // the groups the tiles' blocks ran for these pairs: rows (16 tr) >> o .. of the octave's rows held,
+        // columns (256 tc) >> o .. (a multiple of 4) of its columns, 4 at a time
+        const int r0 = (tr0 * kTileRows) >> o, r1 = std::min((tr1 * kTileRows) >> o, g.oct[o].rows);
+        const int c0 = (tc0 * kTileCols) >> o, c1 = std::min((tc1 * kTileCols) >> o, g.oct[o].cols);
+        g.kp_sg_r0[o] = r0, g.kp_sg_rows[o] = std::max(0, r1 - r0);
+        g.kp_sg_c0[o] = c0, g.kp_sg_gpr[o] = std::max(0, (c1 - c0 + 3) / 4);
+        if (g.kp_sg_rows[o] == 0 || g.kp_sg_gpr[o] == 0) g.kp_sg_rows[o] = g.kp_sg_gpr[o] = 0;
+        per += (long long)g.kp_sg_rows[o] * g.kp_sg_gpr[o];
+        g.kp_sup_begin[o + 1] = (unsigned)std::min<long long>(per, INT32_MAX);
+    }
+    const long long units = (per * g.batch + kTailGroups - 1) / kTailGroups;
+    const bool fits = per * g.batch < (1ll << 31) && units + g.kp_tiles_total + g.kp_tail_units < (1ll << 31);
+    g.kp_sup_units = fits ? (unsigned)units : 0u;
+    g.kp_sup_pad_ = 0;
+}
+
 void set_window_support(gdp_ctx* c, bool on) {
     Geom& g = c->geom;
     if (c->support.size() != (size_t)g.O) {
@@ -591,6 +656,7 @@ void set_window_support(gdp_ctx* c, bool on) {
             og.nz_r0 = og.nzi_r0 = 0, og.nz_r1 = og.nzi_r1 = g.H >> o, og.nz_c0 = 0, og.nz_c1 = og.cols;
         }
     }
+    keep_support_geom(g);
 }
 
 bool valid_level(const gdp_ctx* c, int b, int o, int s) {
@@ -1310,29 +1376,34 @@ int gdp_create_band(gdp_ctx** out, int H, int W, int S, int O, int batch, int ro
     // profiles/ab_sub_c*_r03m.log), 256-thread blocks on small batches, 1024-thread above
     c->inplace_sub = batch == 1 ? 16 : (long long)(row_end - row_begin) * W * batch <= (32ll << 20) ? 4 : 1;
     // Steady-state build (k_keep, GDP_TUNE_KEEP_KERNEL), by pixels per launch — measured on the rotated cold
-    // sets bench.py times, every level-S+2 store made (profiles/keep_kernel_shapes_r08.json; ms for kernel 0 / 1 / 2):
-    //   under 8 Mpix the launch is all ramp and drain and k_build's 16-wave blocks win: 2048^2 0.0145 / 0.0219 /
-    //   0.0156 -> 0;
-    //   up to 64 Mpix 8-wave blocks, 2 rows per wave — more, shorter waves: 4096^2 0.0421 / 0.0381 / 0.0294,
-    //   8 x 1080x1920 0.0435 / 0.0446 / 0.0410, 8192 x 4096 0.0799 / 0.0596 / 0.0540, 4 x 4096^2 0.1576 / 0.1111 /
-    //   0.1037 -> 2;
-    //   above, 4-wave blocks with 4 KiB of loads in flight per wave: 64 x 1080x1920 0.3225 / 0.2520 / 0.2725,
-    //   64 x 4096^2 2.450 / 1.582 / 1.601, 16384^2 0.598 / 0.393 / 0.391 -> 1.
+    // sets bench.py times, with the support units (GDP_TUNE_KEEP_SUPPORT = 1), every level-S+2 store made
+    // (GDP_TUNE_KEEP_SIGNS = 0; profiles/keep_support_r12.json; ms for kernel 0 / 1 / 2):
+    //   under 1.5 Mpix the launch is all ramp and drain and k_build's 16-wave blocks win: 512^2 0.0091 / 0.0105 /
+    //   0.0100, 1024^2 0.0081 / 0.0093 / 0.0094 -> 0;
+    //   up to 64 Mpix 8-wave blocks, 2 rows per wave — more, shorter waves: 1080x1920 0.0106 / 0.0097 / 0.0099 (shape
+    //   1 by 2 %), 2 x 1080x1920 0.0152 / 0.0134 / 0.0116, 2048^2 0.0140 / 0.0134 / 0.0127, 2048 x 4096 0.0244 /
+    //   0.0178 / 0.0163, 8 x 1080x1920 0.0435 / 0.0301 / 0.0306 (shape 1 by 2 %), 4096^2 0.0424 / 0.0285 / 0.0278,
+    //   8192 x 4096 0.0793 / 0.0537 / 0.0519, 4 x 4096^2 0.1578 / 0.1019 / 0.0992 -> 2;
+    //   above, 4-wave blocks with 4 KiB of loads in flight per wave: 64 x 1080x1920 0.3170 / 0.2093 / 0.2194,
+    //   16384^2 0.593 / 0.389 / 0.383 (within 1.5 %; 64 x 4096^2 1.582 / 1.601 before the support units) -> 1.
+    //   (Before the support units the first bound was 8 Mpix: a central tile's groups inside the support ran as
+    //   three to six serial rounds after its block's register pass, and 2048^2 — one round of blocks — took 0.0145 /
+    //   0.0219 / 0.0156.)
     const long long kp_px = (long long)(row_end - row_begin) * W * batch;
-    c->keep_kernel = kp_px < (1ll << 23) ? 0 : kp_px <= (1ll << 26) ? 2 : 1;
+    c->keep_kernel = kp_px < (3ll << 19) ? 0 : kp_px <= (1ll << 26) ? 2 : 1;
     // A launch that skips by the sign map (GDP_TUNE_KEEP_SIGNS, int32 input, the map known) stores next to nothing on non-negative
-    // input, and with no stores to spread over more, shorter waves the 4 rows in flight per wave win wherever k_keep
-    // runs at all (profiles/keep_signs_shapes_r11.json; k_build's keep path cannot skip the stores, so 0 stays 0):
-    //   8 x 1080x1920 0.0432 / 0.0344 / 0.0389, 4096^2 0.0422 / 0.02385 / 0.02383 (a tie), 8192 x 4096 0.0790 / 0.0306 /
-    //   0.0417, 4 x 4096^2 0.158 / 0.0599 / 0.0855, 64 x 1080x1920 0.315 / 0.182 / 0.261, 16384^2 0.597 / 0.164 /
-    //   0.285, 64 x 4096^2 2.44 / 0.774 / 1.31 -> 1.  (2048^2: 0.0140 / 0.0188 / 0.0129; one shape under 8 Mpix is
-    //   not enough to move that threshold.)  Launches that make the stores (uint8 input, GDP_TUNE_KEEP_SIGNS = 0,
-    //   the launch that establishes the map) keep the choice above; a caller's GDP_TUNE_KEEP_KERNEL sets both.
-    //   An image with negative pixels everywhere makes every store in a skipping launch too, and pays for the shape
-    //   that is wrong for stores (all-negative 4096^2: 0.0400 ms on shape 1, 0.0362 on shape 2, the parent 0.0333):
-    //   up to 16 Mpix, where the two shapes tie on non-negative 4096^2, the store-making choice stays (at the cost of
-    //   8 x 1080x1920's 0.0389 instead of 0.0344 ms).
-    c->keep_kernel_signs = (c->keep_kernel > 0 && kp_px <= (1ll << 24)) ? c->keep_kernel : 1;
+    // input, and with no stores to spread over more, shorter waves the 4 rows in flight per wave win from 8 Mpix up
+    // (same file; k_build's keep path cannot skip the stores, so 0 stays 0; ms for kernel 0 / 1 / 2):
+    //   1080x1920 0.0106 / 0.0089 / 0.0088, 2 x 1080x1920 0.0152 / 0.0101 / 0.0097, 2048^2 0.0140 / 0.0107 / 0.0101
+    //   -> up to 4 Mpix the store-making choice stays;
+    //   2048 x 4096 0.0244 / 0.0122 / 0.0127, 8 x 1080x1920 0.0435 / 0.0167 / 0.0249, 4096^2 0.0424 / 0.0148 / 0.0212,
+    //   8192 x 4096 0.0793 / 0.0246 / 0.0382, 4 x 4096^2 0.158 / 0.0446 / 0.0739, 64 x 1080x1920 0.317 / 0.103 / 0.178,
+    //   16384^2 0.593 / 0.158 / 0.281, 64 x 4096^2 2.44 / 0.645 / 1.14 -> 1.
+    //   Launches that make the stores (uint8 input, GDP_TUNE_KEEP_SIGNS = 0, the launch that establishes the map) keep
+    //   the choice above; a caller's GDP_TUNE_KEEP_KERNEL sets both.  An image with negative pixels everywhere makes
+    //   every store in a skipping launch too; with the support units the two shapes tie there (all-negative 4096^2:
+    //   0.0323 ms on either; before them 0.0400 on shape 1, 0.0357 on shape 2, which held this bound at 16 Mpix).
+    c->keep_kernel_signs = (c->keep_kernel > 0 && kp_px <= (1ll << 22)) ? c->keep_kernel : 1;
     // Convolution extension default: block tiles (16 waves) in block order 5 (below; octave-o block
     // rows right after the octave-0 rows that hold their input rows, XCD-chunked) — the fastest form
     // on every config (tools/conv_ab.sh, cold buffers: 4096^2 0.111 ms vs 0.119 for the sweep,
@@ -3992,6 +4063,8 @@ int gdp_get_tuning(const gdp_ctx* c, int key, int* value) try {
         case GDP_TUNE_KEEP_SIGNS: *value = c->keep_signs; return GDP_OK;
         case GDP_TUNE_SIGNS_KNOWN: *value = c->signs_known ? 1 : 0; return GDP_OK;
         case GDP_TUNE_KEEP_SIGNS_KERNEL: *value = c->keep_kernel > 0 ? c->keep_kernel_signs : 0; return GDP_OK;
+        case GDP_TUNE_KEEP_SUPPORT: *value = c->keep_support; return GDP_OK;
+        case GDP_TUNE_KEEP_SUPPORT_UNITS: *value = (int)keep_support_units(c); return GDP_OK;
         default: return GDP_ERR_ARG;
     }
 } GDP_ABI_CATCH(c)
@@ -4084,6 +4157,14 @@ int gdp_set_tuning(gdp_ctx* c, int key, int value) try {
             return c->status(GDP_ERR_ARG, "GDP_TUNE_KEEP_SIGNS_KERNEL is read-only (GDP_TUNE_KEEP_KERNEL sets it)");
         case GDP_TUNE_SIGNS_KNOWN:
             return c->status(GDP_ERR_ARG, "GDP_TUNE_SIGNS_KNOWN is read-only (what clears GDP_TUNE_ZEROS_CLEAN clears it)");
+        case GDP_TUNE_KEEP_SUPPORT:
+            if (value != 0 && value != 1) return c->status(GDP_ERR_ARG, "keep support must be 0 or 1");
+            // a launch-time decision (a kernel argument): no geometry upload, no drain; the same words are
+            // stored either way, so the clean flag and the sign map stay as they are
+            c->keep_support = value;
+            return GDP_OK;
+        case GDP_TUNE_KEEP_SUPPORT_UNITS:
+            return c->status(GDP_ERR_ARG, "GDP_TUNE_KEEP_SUPPORT_UNITS is read-only (GDP_TUNE_KEEP_SUPPORT switches the units)");
         case GDP_TUNE_CONV_ORDER:
             if (value < 0 || value > 7) return c->status(GDP_ERR_ARG, "conv order must be 0..7");
             c->conv_order = value;

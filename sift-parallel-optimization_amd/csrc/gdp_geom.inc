@@ -121,6 +121,18 @@ struct Geom {
     int kp_row_start, kp_pad_; // first tile row that meets some fused octave's support: k_keep's tile order starts there
     unsigned kp_tiles_per_img, kp_tiles_total;
     unsigned kp_tail_groups_per_img, kp_tail_units;
+    // k_keep's support units (GDP_TUNE_KEEP_SUPPORT), set with the support (set_window_support).  Per
+    // fused octave o < kp_F the tiles whose footprint meets the support (OctGeom::sp_*) are the
+    // rectangle of tile rows [kp_sl_tr0, kp_sl_tr1) x tile columns [kp_sl_tc0, kp_sl_tc1) (band-local
+    // tile rows; empty: tr0 == tr1): the kernel classifies a (tile, octave) pair by these alone.  The
+    // octave's footprint of that rectangle, clipped to the rows and columns the context holds, in
+    // 4-pixel groups: kp_sg_rows rows from band-local octave row kp_sg_r0, kp_sg_gpr groups per row
+    // from column kp_sg_c0.  kp_sup_begin: prefix over the fused octaves of rows * gpr per image;
+    // kp_sup_units: 256-group slices of [batch][kp_sup_begin[kp_F]].
+    int kp_sl_tr0[kFused], kp_sl_tr1[kFused], kp_sl_tc0[kFused], kp_sl_tc1[kFused];
+    int kp_sg_r0[kFused], kp_sg_rows[kFused], kp_sg_c0[kFused], kp_sg_gpr[kFused];
+    unsigned kp_sup_begin[kFused + 1];
+    unsigned kp_sup_units, kp_sup_pad_;
     OctGeom oct[kMaxOct];
     unsigned lv_blk[kMaxOct + 1]; // prefix over octaves of ceil(rows*gpr / kLevBlock) per image
     unsigned lx_blk[kMaxOct + 1]; // prefix over octaves of ceil(rows*gpr / 64) per image (k_levels_x)

@@ -64,6 +64,32 @@ __device__ __forceinline__ void keep_tail_unit(const Geom* __restrict__ g, const
     }
 }
 
+// Support unit `su` (GDP_TUNE_KEEP_SUPPORT): 256 consecutive groups of the fused octaves' support
+// rectangles (Geom::kp_sg_*: the groups of every (tile, octave) pair whose footprint meets the
+// support), flattened per image over the batch — the tail units' walk on another prefix, one group
+// per thread on either block shape, every group through build_group's keep path as in the tile's
+// own block before.
+template <bool NT>
+__device__ __forceinline__ void keep_support_unit(const Geom* __restrict__ g, const void* __restrict__ in,
+                                                  float* __restrict__ out, const float* __restrict__ taps, unsigned su) {
+    if (threadIdx.x >= kTailGroups) return;
+    const int F = g->kp_F;
+    const unsigned t = su * kTailGroups + threadIdx.x;
+    const unsigned per = g->kp_sup_begin[F];
+    if (t >= per * (unsigned)g->batch) return;
+    const unsigned b = t / per;
+    const unsigned rem = t - b * per;
+    int o = 0;
+    while (o + 1 < F && rem >= g->kp_sup_begin[o + 1]) ++o;
+    const OctGeom og = g->oct[o];
+    const int k = (int)(rem - g->kp_sup_begin[o]);
+    const int gpr = g->kp_sg_gpr[o];
+    const int r = k / gpr;
+    const int Rl = g->kp_sg_r0[o] + r;
+    const int C = g->kp_sg_c0[o] + 4 * (k - r * gpr);
+    build_group<0, NT, false>(g, in, out, taps, 1, (int)b, o, og, Rl, C);
+}
+
 // The register stores of one tile: wave w owns tile rows w RPL .. w RPL + RPL - 1, lane l columns
 // 4 l .. 4 l + 3 of each.  Every load of the lane is issued before its first store (RPL KiB in
 // flight per wave); a row or column beyond the image is clamped for the load (always in bounds, no
@@ -183,52 +209,68 @@ __device__ __forceinline__ void keep_tile_fast(const Geom* __restrict__ g, const
     for (int j = 0; j < RPL; ++j) store_row(j);
 }
 
-// Work units: [0, kp_tiles_total) are kTileRows x kTileCols input tiles, [kp_tiles_total,
-// +kp_tail_units) 256-group slices of the octaves >= kp_F — a grid of its own, whatever build
+// Work units: the support units (below) if any, then kp_tiles_total kTileRows x kTileCols input
+// tiles, then kp_tail_units 256-group slices of the octaves >= kp_F — a grid of its own, whatever build
 // variant is selected.  A block is kTileRows / RPL waves.  The host takes this kernel only when
 // W % 4 == 0 and the input allows one vector load per 4 pixels, so every group is whole and every
 // store aligned.  Per (tile, octave), wave-uniformly: the octave's footprint of the tile misses the
-// support (OctGeom::sp_*) -> the register stores above; else that octave's groups of the tile go
-// through build_group's keep path, which tests each group and is exact by construction.
+// support (OctGeom::sp_*; the host's tile rectangles Geom::kp_sl_*) -> the register stores above;
+// else that octave's groups of the tile go through build_group's keep path, which tests each group
+// and is exact by construction.  `support` != 0 (GDP_TUNE_KEEP_SUPPORT, a launch-time argument):
+// those groups — at 4096^2 a central tile's 1364, three to six serial rounds of dependent loads and
+// stores after the block's register pass — run as units of their own, [0, kp_sup_units) ahead of the
+// tiles, one group per thread, and a tile's block does nothing for the octaves that meet the support.
+// The same words from the same pixels by the same code either way.
 template <bool NT, int RPL, bool SIGNS>
 __global__ void __launch_bounds__(64 * kTileRows / RPL) k_keep(const Geom* __restrict__ g, const void* __restrict__ in,
                                                                float* __restrict__ out, const float* __restrict__ taps,
-                                                               unsigned char* sign_map, int signs) {
+                                                               int support, unsigned char* sign_map, int signs) {
     constexpr int BLK = 64 * kTileRows / RPL;
     static_assert(kTileCols == 256 && kTileRows == 16 && kFused == 5 && kTileRows % RPL == 0, "k_keep's tile");
-    const unsigned tiles_total = g->kp_tiles_total;
-    const unsigned units = tiles_total + g->kp_tail_units;
+    static_assert(BLK >= kTailGroups, "a support unit is one group per thread");
+    // Units: [0, sup_units) the support units — first, so they are dispatched first —, then the
+    // tiles, then the tail units.  `support` = 0 (GDP_TUNE_KEEP_SUPPORT = 0), or no unit at all: the
+    // groups inside the support stay in their tiles' blocks (below).
+    const unsigned sup_units = support ? g->kp_sup_units : 0u;
+    const unsigned tiles_end = sup_units + g->kp_tiles_total;
+    const unsigned units = tiles_end + g->kp_tail_units;
     const int F = g->kp_F;
     for (unsigned u = blockIdx.x; u < units; u += gridDim.x) {
-        if (u >= tiles_total) {
-            keep_tail_unit<NT, BLK>(g, in, out, taps, u - tiles_total);
+        if (u < sup_units) {
+            keep_support_unit<NT>(g, in, out, taps, u);
             continue;
         }
-        // Tile order: each image's tile rows in order, but starting at the first row that meets the
-        // support (kp_row_start) and wrapping round.  The few tiles inside the support take the
-        // per-group path below — chains of dependent loads and stores several times a register
-        // tile's life — so they start early and run under the rest of the launch instead of
-        // extending its end; the stream stays linear but for one wrap.  Any order gives the same bits.
-        const unsigned b = u / g->kp_tiles_per_img;
-        const unsigned rem = u - b * g->kp_tiles_per_img;
+        if (u >= tiles_end) {
+            keep_tail_unit<NT, BLK>(g, in, out, taps, u - tiles_end);
+            continue;
+        }
+        // Tile order.  With support units: plain linear.  Without: each image's tile rows in order,
+        // but starting at the first row that meets the support (kp_row_start) and wrapping round — the
+        // few tiles inside the support then take the per-group path below, chains of dependent loads
+        // and stores several times a register tile's life, so they start early and run under the rest
+        // of the launch instead of extending its end.  Any order gives the same bits.
+        const unsigned ut = u - sup_units;
+        const unsigned b = ut / g->kp_tiles_per_img;
+        const unsigned rem = ut - b * g->kp_tiles_per_img;
         const unsigned kr = rem / (unsigned)g->kp_tiles_c;
         const unsigned tc = rem - kr * (unsigned)g->kp_tiles_c;
         const unsigned tiles_r = g->kp_tiles_per_img / (unsigned)g->kp_tiles_c;
-        const unsigned tr = kr + (unsigned)g->kp_row_start < tiles_r ? kr + (unsigned)g->kp_row_start
-                                                                      : kr + (unsigned)g->kp_row_start - tiles_r;
+        const unsigned row_start = sup_units ? 0u : (unsigned)g->kp_row_start;
+        const unsigned tr = kr + row_start < tiles_r ? kr + row_start : kr + row_start - tiles_r;
         const int in_r0 = (int)tr * kTileRows; // band-local input row of the tile (in_row0 is a multiple of 16)
         const int in_c0 = (int)tc * kTileCols;
-        // the octaves whose footprint of this tile lies outside the support, and level S+2 of each
-        // (oct[o] beyond O is all zero: no rows, nothing stored)
+        // the octaves whose footprint of this tile lies outside the support: the tile is outside the
+        // host's rectangle of tiles that meet it (Geom::kp_sl_*, the same intervals the support units
+        // are cut from, so the two cannot disagree); and level S+2 of each (oct[o] beyond O is all
+        // zero: no rows, nothing stored)
         unsigned fast = 0;
         int rows[kFused], cols[kFused];
         long long off[kFused];
 #pragma unroll
         for (int o = 0; o < kFused; ++o) {
             const OctGeom& og = g->oct[o];
-            const int r_lo = og.row0 + (in_r0 >> o), r_hi = r_lo + (kTileRows >> o);
-            const int c_lo = in_c0 >> o, c_hi = min(c_lo + (kTileCols >> o), og.cols);
-            const bool hit = r_lo < og.sp_r1 && r_hi > og.sp_r0 && c_lo < og.sp_c1 && c_hi > og.sp_c0;
+            const bool hit = (int)tr >= g->kp_sl_tr0[o] && (int)tr < g->kp_sl_tr1[o] && (int)tc >= g->kp_sl_tc0[o] &&
+                             (int)tc < g->kp_sl_tc1[o];
             if (o < F && !hit) fast |= 1u << o;
             rows[o] = og.rows;
             cols[o] = og.cols;
@@ -245,7 +287,7 @@ __global__ void __launch_bounds__(64 * kTileRows / RPL) k_keep(const Geom* __res
                 keep_tile_fast<NT, RPL, true, SIGNS>(g, in, img_out, b, in_r0, in_c0, fast, rows, cols, off, flags, signs);
         }
         const unsigned slow = ~fast & ((1u << F) - 1u);
-        if (!slow) continue;
+        if (!slow || sup_units) continue;  // with support units those groups are theirs
         // the groups of the other octaves, flattened over the block's threads (octave o of a tile is
         // (16 >> o) rows of (64 >> o) groups): as few rounds of build_group as the block allows
         int total = 0;
@@ -273,7 +315,7 @@ __global__ void __launch_bounds__(64 * kTileRows / RPL) k_keep(const Geom* __res
 // GDP_TUNE_KEEP_KERNEL values >= 1: rows per lane (block = 16 / rows waves); all bit-identical.
 struct KeepKernel {
     int id, block;
-    void (*k[2][2])(const Geom*, const void*, float*, const float*, unsigned char*, int); // [uses the sign map][NT]
+    void (*k[2][2])(const Geom*, const void*, float*, const float*, int, unsigned char*, int); // [uses the sign map][NT]
 };
 #define GDP_KEEP_KERNEL(ID, RPL)                                                      \
     KeepKernel {                                                                      \

@@ -363,8 +363,9 @@ class PyramidContext:
 
     _TUNING = ("nontemporal", "blocks_per_cu", "grid", "variant", "tile_order", "inplace_sub", "window_sub",
                "conv_kernel", "conv_rows", "conv_order", "build_lds", "stage_kb", "stage_threads", "conv_waves", "zero_window",
-               "store_pace", "conv_pace", "inplace_pace", "keep_zeros", "keep_kernel", "keep_signs",
-               "pyramid_chunk_kb", "zeros_clean", "signs_known", "keep_signs_kernel")  # the last four read-only
+               "store_pace", "conv_pace", "inplace_pace", "keep_zeros", "keep_kernel", "keep_signs", "keep_support",
+               "pyramid_chunk_kb", "zeros_clean", "signs_known", "keep_signs_kernel",
+               "keep_support_units")  # the last five read-only
 
     @staticmethod
     def _tuning_key(name):
@@ -376,7 +377,7 @@ class PyramidContext:
                    inplace_sub=None, window_sub=None, conv_kernel=None, conv_rows=None, conv_order=None,
                    build_lds=None, stage_kb=None, stage_threads=None, conv_waves=None, zero_window=None,
                    store_pace=None, conv_pace=None, inplace_pace=None, keep_zeros=None,
-                   keep_kernel=None, keep_signs=None):
+                   keep_kernel=None, keep_signs=None, keep_support=None):
         """Performance knobs of the kernels (outputs are bit-identical for every setting; the
         conv_* knobs select the convolution extension's kernel: 0 register sweep, 1 LDS tiles,
         2 block tiles, and the sweep's rows per wave strip (16 / 32) or the block tiles' rows per
@@ -393,13 +394,15 @@ class PyramidContext:
         4 / 2 rows per wave, taken where the width is a multiple of 4; keep_signs = 0 makes every
         such build store all of level S+2 = copysign(0, x), instead of skipping the tile rows that
         held no negative int32 pixel at this build and the one before —
-        tuning()["signs_known"] tells whether the next one may skip)."""
+        tuning()["signs_known"] tells whether the next one may skip; keep_support = 0 makes the
+        steady-state kernel run the groups inside the windows' support in their tiles' blocks instead
+        of as work units of their own — tuning()["keep_support_units"] counts them)."""
         vals = dict(nontemporal=nontemporal, blocks_per_cu=blocks_per_cu, grid=grid, variant=variant,
                     tile_order=tile_order, inplace_sub=inplace_sub, window_sub=window_sub, conv_kernel=conv_kernel,
                     conv_rows=conv_rows, conv_order=conv_order, build_lds=build_lds, stage_kb=stage_kb,
                     stage_threads=stage_threads, conv_waves=conv_waves, zero_window=zero_window,
                     store_pace=store_pace, conv_pace=conv_pace, inplace_pace=inplace_pace, keep_zeros=keep_zeros,
-                    keep_kernel=keep_kernel, keep_signs=keep_signs)
+                    keep_kernel=keep_kernel, keep_signs=keep_signs, keep_support=keep_support)
         for name, val in vals.items():
             if val is not None:
                 check(lib().gdp_set_tuning(self._ctx, self._tuning_key(name), int(val)), self._ctx)

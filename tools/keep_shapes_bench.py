@@ -7,7 +7,9 @@ Per shape (5 octaves, S = 2, bench.py's synthetic non-negative int32 image): eno
 as in bench.py, and per round and mode three untimed builds of every context, then `iters` rotated builds between two
 events on the launch stream; `--rounds` alternated rounds, median and range per mode.  Modes: kk0 / kk1 / kk2
 GDP_TUNE_KEEP_KERNEL 0 / 1 / 2 (an explicit value also sets the shape of the launches that skip by the sign map); ks0
-GDP_TUNE_KEEP_SIGNS = 0 on the default kernel; kz0 GDP_TUNE_KEEP_ZEROS = 0 (the full build); def the library's defaults.
+GDP_TUNE_KEEP_SIGNS = 0 on the default kernel; kz0 GDP_TUNE_KEEP_ZEROS = 0 (the full build); def the library's defaults;
+sup0 GDP_TUNE_KEEP_SUPPORT = 0 on the default kernel, kk1s0 / kk2s0 on kernel 1 / 2 (every other mode leaves that knob at its default); kk1ks0 / kk2ks0 kernel 1 / 2 with
+GDP_TUNE_KEEP_SIGNS = 0: launches that make every level-S+2 store.
 --tree: another checkout (built) to import the package from, e.g. the parent commit's, for the same table of it."""
 import argparse, json, os, statistics, sys
 
@@ -24,7 +26,9 @@ import __graft_entry__ as entry  # noqa
 
 pkg = entry.load_package()
 MODES = {"kk0": dict(keep_kernel=0), "kk1": dict(keep_kernel=1), "kk2": dict(keep_kernel=2), "def": {},
-         "ks0": dict(keep_signs=0), "kz0": dict(keep_zeros=0)}
+         "ks0": dict(keep_signs=0), "kz0": dict(keep_zeros=0), "sup0": dict(keep_support=0),
+         "kk1s0": dict(keep_kernel=1, keep_support=0), "kk2s0": dict(keep_kernel=2, keep_support=0),
+         "kk1ks0": dict(keep_kernel=1, keep_signs=0), "kk2ks0": dict(keep_kernel=2, keep_signs=0)}
 res = {}
 stream = torch.cuda.Stream()
 for shape in a.shapes.split(","):
@@ -45,6 +49,8 @@ for shape in a.shapes.split(","):
             knobs = dict(keep_kernel=base["keep_kernel"], keep_zeros=1)
             if "keep_signs" in base:
                 knobs["keep_signs"] = 1
+            if "keep_support" in base:
+                knobs["keep_support"] = base["keep_support"]
             knobs.update(MODES[m])
             for c in ctxs:
                 c.set_tuning(**knobs)
