@@ -266,11 +266,36 @@ protected:
         SyncHost();
     }
     static void check_(gdp_ctx* c, int status, const char* what) {
-        if (status != GDP_OK) {
-            std::fprintf(stderr, "GaussPyramid_hip::%s failed: %s (%s)\n", what, gdp_status_string(status),
-                         gdp_last_error(c));
-            std::abort();
-        }
+        if (status != GDP_OK) fail_(what, gdp_last_error(c), status);
+    }
+    // every failure ends here, with the last-error text of the object the call was made on
+    [[noreturn]] static void fail_(const char* what, const char* last, int status) {
+        std::fprintf(stderr, "GaussPyramid_hip::%s failed: %s (%s)\n", what, gdp_status_string(status), last);
+        std::abort();
+    }
+    // a stage object's call: its text is asked for after the call, from `h` (NULL for a failed create)
+    template <class H>
+    static void check_(const char* what, const char* last_error(const H*), const H* h, int status) {
+        if (status != GDP_OK) fail_(what, last_error(h), status);
+    }
+    void ensure_described_(const char* what) {  // a pyramid that was never described has an empty list
+        if (!orient_) check_<gdp_orient>(what, gdp_orient_last_error, nullptr, gdp_orient_create(&orient_, ctx_, 0));
+        if (!describe_)
+            check_<gdp_describe>(what, gdp_describe_last_error, nullptr, gdp_describe_create(&describe_, ctx_, orient_, 0));
+    }
+    // count, size the vector, download, resize to what was stored; `lead` is the image of a per-image list
+    template <class Rec, class H, class Count, class Download, class... Lead>
+    static std::vector<Rec> list_(const char* what, const char* last_error(const H*), H* h, Count count, Download download,
+                                  Lead... lead) {
+        size_t found = 0, stored = 0;
+        check_(what, last_error, h, count(h, lead..., &found));
+        std::vector<Rec> out(found);
+        check_(what, last_error, h, download(h, lead..., out.data(), out.size(), &stored, nullptr));
+        out.resize(stored);
+        return out;
+    }
+    static int download_refined_(gdp_ctx* c, int b, gdp_keypoint_refined* host, size_t capacity, size_t* stored, size_t*) {
+        return gdp_download_refined(c, b, host, capacity, stored);  // the one list without a `found` output
     }
 };
 
@@ -425,12 +450,7 @@ inline std::vector<gdp_keypoint> GaussPyramid_hip::DetectExtrema(float contrast_
     pull_host_();
     armed_ = clean;  // the detection leaves the device pyramid alone: the record of written pages stays valid
     check_(ctx_, gdp_detect_extrema(ctx_, contrast_threshold, edge_ratio, nullptr), "DetectExtrema");
-    size_t found = 0, stored = 0;
-    check_(ctx_, gdp_keypoint_count(ctx_, 0, &found), "DetectExtrema");
-    std::vector<gdp_keypoint> out(found);
-    check_(ctx_, gdp_download_keypoints(ctx_, 0, out.data(), out.size(), &stored, nullptr), "DetectExtrema");
-    out.resize(stored);
-    return out;
+    return list_<gdp_keypoint>("DetectExtrema", gdp_last_error, ctx_, gdp_keypoint_count, gdp_download_keypoints, 0);
 }
 
 inline std::vector<gdp_keypoint_refined> GaussPyramid_hip::RefineKeypoints(float contrast, float edge_ratio) {
@@ -439,110 +459,60 @@ inline std::vector<gdp_keypoint_refined> GaussPyramid_hip::RefineKeypoints(float
     pull_host_();
     armed_ = clean;  // the refinement leaves the device pyramid alone, like the detection
     check_(ctx_, gdp_refine_keypoints(ctx_, contrast, edge_ratio, nullptr), "RefineKeypoints");
-    size_t kept = 0, stored = 0;
-    check_(ctx_, gdp_refined_count(ctx_, 0, &kept), "RefineKeypoints");
-    std::vector<gdp_keypoint_refined> out(kept);
-    check_(ctx_, gdp_download_refined(ctx_, 0, out.data(), out.size(), &stored), "RefineKeypoints");
-    out.resize(stored);
-    return out;
+    return list_<gdp_keypoint_refined>("RefineKeypoints", gdp_last_error, ctx_, gdp_refined_count, download_refined_, 0);
 }
 
 inline std::vector<gdp_keypoint_oriented> GaussPyramid_hip::OrientKeypoints() {
+    const char* const what = "OrientKeypoints";
     CallScope scope(this);
     const bool clean = armed_;
     pull_host_();
     armed_ = clean;  // the orientation leaves the device pyramid alone, like the detection
-    auto check = [](gdp_orient* w, int status) {
-        if (status != GDP_OK) {
-            std::fprintf(stderr, "GaussPyramid_hip::OrientKeypoints failed: %s (%s)\n", gdp_status_string(status),
-                         gdp_orient_last_error(w));
-            std::abort();
-        }
-    };
-    if (!orient_) check(nullptr, gdp_orient_create(&orient_, ctx_, 0));
-    check(orient_, gdp_orient_keypoints(orient_, nullptr));
-    size_t found = 0, stored = 0;
-    check(orient_, gdp_oriented_count(orient_, 0, &found));
-    std::vector<gdp_keypoint_oriented> out(found);
-    check(orient_, gdp_download_oriented(orient_, 0, out.data(), out.size(), &stored, nullptr));
-    out.resize(stored);
-    return out;
+    if (!orient_) check_<gdp_orient>(what, gdp_orient_last_error, nullptr, gdp_orient_create(&orient_, ctx_, 0));
+    check_(what, gdp_orient_last_error, orient_, gdp_orient_keypoints(orient_, nullptr));
+    return list_<gdp_keypoint_oriented>(what, gdp_orient_last_error, orient_, gdp_oriented_count, gdp_download_oriented, 0);
 }
 
 inline std::vector<gdp_keypoint_described> GaussPyramid_hip::DescribeKeypoints() {
+    const char* const what = "DescribeKeypoints";
     CallScope scope(this);
     const bool clean = armed_;
     pull_host_();
     armed_ = clean;  // the description leaves the device pyramid alone, like the detection
-    auto check = [](const char* last, int status) {
-        if (status != GDP_OK) {
-            std::fprintf(stderr, "GaussPyramid_hip::DescribeKeypoints failed: %s (%s)\n", gdp_status_string(status), last);
-            std::abort();
-        }
-    };
-    if (!orient_) check(gdp_orient_last_error(nullptr), gdp_orient_create(&orient_, ctx_, 0));
-    if (!describe_) check(gdp_describe_last_error(nullptr), gdp_describe_create(&describe_, ctx_, orient_, 0));
-    check(gdp_describe_last_error(describe_), gdp_describe_keypoints(describe_, nullptr));
-    size_t found = 0, stored = 0;
-    check(gdp_describe_last_error(describe_), gdp_described_count(describe_, 0, &found));
-    std::vector<gdp_keypoint_described> out(found);
-    check(gdp_describe_last_error(describe_), gdp_download_described(describe_, 0, out.data(), out.size(), &stored, nullptr));
-    out.resize(stored);
-    return out;
+    ensure_described_(what);
+    check_(what, gdp_describe_last_error, describe_, gdp_describe_keypoints(describe_, nullptr));
+    return list_<gdp_keypoint_described>(what, gdp_describe_last_error, describe_, gdp_described_count, gdp_download_described, 0);
 }
 
 inline std::vector<gdp_match_record> GaussPyramid_hip::MatchDescriptors(GaussPyramid_hip& other, float ratio, uint32_t max_distance,
                                                                         bool mutual) {
-    auto check = [](const char* last, int status) {
-        if (status != GDP_OK) {
-            std::fprintf(stderr, "GaussPyramid_hip::MatchDescriptors failed: %s (%s)\n", gdp_status_string(status), last);
-            std::abort();
-        }
-    };
-    for (GaussPyramid_hip* g : {this, &other}) {  // a pyramid that was never described has an empty list
-        if (!g->orient_) check(gdp_orient_last_error(nullptr), gdp_orient_create(&g->orient_, g->ctx_, 0));
-        if (!g->describe_) check(gdp_describe_last_error(nullptr), gdp_describe_create(&g->describe_, g->ctx_, g->orient_, 0));
-    }
+    const char* const what = "MatchDescriptors";
+    ensure_described_(what);
+    other.ensure_described_(what);
     gdp_match* m = nullptr;
-    check(gdp_match_last_error(nullptr), gdp_match_create(&m, describe_, other.describe_, 0, 0));
+    check_<gdp_match>(what, gdp_match_last_error, nullptr, gdp_match_create(&m, describe_, other.describe_, 0, 0));
     // DescribeKeypoints ends in a blocking download, so nothing of `other` is still in flight on its stream
-    check(gdp_match_last_error(m), gdp_match_descriptors(m, 0, 0, ratio, max_distance, mutual ? 1 : 0, nullptr));
-    size_t found = 0, stored = 0;
-    check(gdp_match_last_error(m), gdp_match_count(m, &found));
-    std::vector<gdp_match_record> out(found);
-    check(gdp_match_last_error(m), gdp_download_matches(m, out.data(), out.size(), &stored, nullptr));
-    out.resize(stored);
+    check_(what, gdp_match_last_error, m, gdp_match_descriptors(m, 0, 0, ratio, max_distance, mutual ? 1 : 0, nullptr));
+    std::vector<gdp_match_record> out = list_<gdp_match_record>(what, gdp_match_last_error, m, gdp_match_count, gdp_download_matches);
     gdp_match_destroy(m);
     return out;
 }
 
 inline gdp_homography GaussPyramid_hip::FitHomography(const std::vector<gdp_match_record>& matches, std::vector<gdp_match_record>* inliers,
                                                       uint32_t hypotheses, uint32_t seed, float threshold, uint32_t min_inliers) {
-    auto check = [](const char* last, int status) {
-        if (status != GDP_OK) {
-            std::fprintf(stderr, "GaussPyramid_hip::FitHomography failed: %s (%s)\n", gdp_status_string(status), last);
-            std::abort();
-        }
-    };
-    if (!orient_) check(gdp_orient_last_error(nullptr), gdp_orient_create(&orient_, ctx_, 0));
-    if (!describe_) check(gdp_describe_last_error(nullptr), gdp_describe_create(&describe_, ctx_, orient_, 0));
+    const char* const what = "FitHomography";
+    ensure_described_(what);
     const size_t n = matches.size(), cap = n ? n : 1;
     gdp_match* m = nullptr;  // the fit object is made from a match object; its own list is never read here
-    check(gdp_match_last_error(nullptr), gdp_match_create(&m, describe_, describe_, cap, 1));
+    check_<gdp_match>(what, gdp_match_last_error, nullptr, gdp_match_create(&m, describe_, describe_, cap, 1));
     gdp_ransac* r = nullptr;
-    check(gdp_ransac_last_error(nullptr), gdp_ransac_create(&r, m, cap, hypotheses));
+    check_<gdp_ransac>(what, gdp_ransac_last_error, nullptr, gdp_ransac_create(&r, m, cap, hypotheses));
     const gdp_match_record none{};
-    check(gdp_ransac_last_error(r), gdp_ransac_set_input(r, n ? matches.data() : &none, n));
-    check(gdp_ransac_last_error(r), gdp_fit_homography(r, hypotheses, seed, threshold, min_inliers, nullptr));
+    check_(what, gdp_ransac_last_error, r, gdp_ransac_set_input(r, n ? matches.data() : &none, n));
+    check_(what, gdp_ransac_last_error, r, gdp_fit_homography(r, hypotheses, seed, threshold, min_inliers, nullptr));
     gdp_homography model;
-    check(gdp_ransac_last_error(r), gdp_download_homography(r, &model));
-    if (inliers) {
-        size_t found = 0, stored = 0;
-        check(gdp_ransac_last_error(r), gdp_ransac_count(r, &found));
-        inliers->resize(found);
-        check(gdp_ransac_last_error(r), gdp_download_inliers(r, inliers->data(), inliers->size(), &stored, nullptr));
-        inliers->resize(stored);
-    }
+    check_(what, gdp_ransac_last_error, r, gdp_download_homography(r, &model));
+    if (inliers) *inliers = list_<gdp_match_record>(what, gdp_ransac_last_error, r, gdp_ransac_count, gdp_download_inliers);
     gdp_ransac_destroy(r);
     gdp_match_destroy(m);
     return model;
@@ -550,29 +520,22 @@ inline gdp_homography GaussPyramid_hip::FitHomography(const std::vector<gdp_matc
 
 inline std::vector<int32_t> GaussPyramid_hip::WarpImage(GaussPyramid_hip& other, const float h[9], int direction, int32_t fill,
                                                         gdp_warp_record* record, int* rows, int* cols) {
-    auto check = [](const char* last, int status) {
-        if (status != GDP_OK) {
-            std::fprintf(stderr, "GaussPyramid_hip::WarpImage failed: %s (%s)\n", gdp_status_string(status), last);
-            std::abort();
-        }
-    };
-    for (GaussPyramid_hip* g : {this, &other}) {
-        if (!g->orient_) check(gdp_orient_last_error(nullptr), gdp_orient_create(&g->orient_, g->ctx_, 0));
-        if (!g->describe_) check(gdp_describe_last_error(nullptr), gdp_describe_create(&g->describe_, g->ctx_, g->orient_, 0));
-    }
+    const char* const what = "WarpImage";
+    ensure_described_(what);
+    other.ensure_described_(what);
     gdp_match* m = nullptr;  // the warp object reaches the two contexts through a fit and a match object; no list is read
-    check(gdp_match_last_error(nullptr), gdp_match_create(&m, describe_, other.describe_, 1, 1));
+    check_<gdp_match>(what, gdp_match_last_error, nullptr, gdp_match_create(&m, describe_, other.describe_, 1, 1));
     gdp_ransac* r = nullptr;
-    check(gdp_ransac_last_error(nullptr), gdp_ransac_create(&r, m, 1, 1));
+    check_<gdp_ransac>(what, gdp_ransac_last_error, nullptr, gdp_ransac_create(&r, m, 1, 1));
     gdp_warp* w = nullptr;
-    check(gdp_warp_last_error(nullptr), gdp_warp_create(&w, r));
-    check(gdp_warp_last_error(w), gdp_warp_set_model(w, h));
-    check(gdp_warp_last_error(w), gdp_warp_image(w, direction, 0, 0, fill, nullptr));
+    check_<gdp_warp>(what, gdp_warp_last_error, nullptr, gdp_warp_create(&w, r));
+    check_(what, gdp_warp_last_error, w, gdp_warp_set_model(w, h));
+    check_(what, gdp_warp_last_error, w, gdp_warp_image(w, direction, 0, 0, fill, nullptr));
     int height = 0, width = 0;
-    check(gdp_warp_last_error(w), gdp_device_warped(w, nullptr, nullptr, &height, &width, nullptr, nullptr));
+    check_(what, gdp_warp_last_error, w, gdp_device_warped(w, nullptr, nullptr, &height, &width, nullptr, nullptr));
     std::vector<int32_t> out((size_t)height * (size_t)width);
-    check(gdp_warp_last_error(w), gdp_download_warped(w, out.data(), (size_t)width));
-    if (record) check(gdp_warp_last_error(w), gdp_download_warp_record(w, record));
+    check_(what, gdp_warp_last_error, w, gdp_download_warped(w, out.data(), (size_t)width));
+    if (record) check_(what, gdp_warp_last_error, w, gdp_download_warp_record(w, record));
     if (rows) *rows = height;
     if (cols) *cols = width;
     gdp_warp_destroy(w);

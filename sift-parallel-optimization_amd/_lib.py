@@ -1,7 +1,9 @@
 """ctypes binding of libgdp.so — the C ABI declared in include/gdp.h.
 
 The product path is the HIP library; there is no CPU fallback.  If libgdp.so is missing or a
-call fails, this module raises GdpError — loudly, never silently computing elsewhere.
+call fails, this module raises GdpError — loudly, never silently computing elsewhere: check() turns a
+status into the error, with the last error text of the object the call was made on (LAST_ERROR names
+the export per kind of handle: the context and the five stage objects).
 
 HIP runtime sharing: the PyTorch-ROCm wheel ships its own libamdhip64.so (soname
 libamdhip64.so.7).  libgdp.so needs `libamdhip64.so.7`; when torch is imported FIRST, the dynamic
@@ -241,20 +243,17 @@ def build_variants():
     return list(ids)
 
 
-def check(status, ctx=None, orient=False, describe=False, match=False, ransac=False, warp=False):
-    """Raise GdpError for a non-zero status; `ctx` is the context whose gdp_last_error describes it
-    (orient=True: a gdp_orient object, or None for a failed gdp_orient_create; describe=True,
-    match=True, ransac=True and warp=True: the same for a gdp_describe, a gdp_match, a gdp_ransac and
-    a gdp_warp object)."""
+# handle kind -> the export that holds its last error text
+LAST_ERROR = {"ctx": "gdp_last_error", "orient": "gdp_orient_last_error", "describe": "gdp_describe_last_error",
+              "match": "gdp_match_last_error", "ransac": "gdp_ransac_last_error", "warp": "gdp_warp_last_error"}
+
+
+def check(status, handle=None, kind="ctx"):
+    """Raise GdpError for a non-zero status.  `handle` is the object the failed call was made on, or
+    None for a failed create, and `kind` names what it is (a key of LAST_ERROR; an unknown one is a
+    KeyError): the message is that object's last error text, else gdp_status_string(status)."""
+    last_error = LAST_ERROR[kind]
     if status != GDP_OK:
         L = lib()
-        if warp:
-            msg = L.gdp_warp_last_error(ctx)
-        elif ransac:
-            msg = L.gdp_ransac_last_error(ctx)
-        elif match:
-            msg = L.gdp_match_last_error(ctx)
-        else:
-            msg = L.gdp_describe_last_error(ctx) if describe else L.gdp_orient_last_error(ctx) if orient else L.gdp_last_error(ctx)
-        raise GdpError(status, (msg or b"").decode() or L.gdp_status_string(status).decode())
+        raise GdpError(status, (getattr(L, last_error)(handle) or b"").decode() or L.gdp_status_string(status).decode())
     return status

@@ -43,6 +43,7 @@ row band), used by bench.py and the multi-GPU driver.
 import ctypes
 import sys
 import weakref
+from collections import namedtuple
 
 import numpy as np
 
@@ -120,6 +121,56 @@ class Keypoints(np.ndarray):
         self.found = getattr(obj, "found", 0)
 
 
+# The five stage objects a context creates on first use, upstream first, keyed by their kind (the
+# name check() reports their errors under): the create and destroy exports, whether the create takes
+# the context, and the object it reads — that one is created before it and destroyed after it.
+_Object = namedtuple("_Object", "create destroy takes_ctx reads")
+_OBJECTS = {"orient": _Object("gdp_orient_create", "gdp_orient_destroy", True, None),
+            "describe": _Object("gdp_describe_create", "gdp_describe_destroy", True, "orient"),
+            "match": _Object("gdp_match_create", "gdp_match_destroy", False, "describe"),  # and the train side's
+            "ransac": _Object("gdp_ransac_create", "gdp_ransac_destroy", False, "match"),
+            "warp": _Object("gdp_warp_create", "gdp_warp_destroy", False, "ransac")}
+
+
+# The list operations every stage has, each once: `export` is called on `handle` (the context or a
+# stage object of `kind`) with the leading arguments `lead`: (image,), (side,) or ().
+def _count(export, handle, lead, kind):
+    n = ctypes.c_size_t()
+    check(getattr(lib(), export)(handle, *lead, ctypes.byref(n)), handle, kind)
+    return n.value
+
+
+def _download(export, handle, lead, kind, dtype, room, found=True):
+    """Download into `room` records and trim to the stored ones; where the export reports `found`,
+    the result is a Keypoints view that carries it."""
+    out = np.zeros(room, dtype)
+    tail = [ctypes.c_size_t() for _ in range(2 if found else 1)]  # stored[, found]
+    check(getattr(lib(), export)(handle, *lead, _ptr(out) if out.size else None, out.size, *map(ctypes.byref, tail)),
+          handle, kind)
+    out = out[:tail[0].value]
+    if found:
+        out = out.view(Keypoints)
+        out.found = tail[1].value
+    return out
+
+
+def _device_pointers(export, handle, lead, kind, n=2):
+    """The device addresses the export gives: (records, their uint32 counter[, ...])."""
+    ptrs = [ctypes.c_void_p() for _ in range(n)]
+    check(getattr(lib(), export)(handle, *lead, *map(ctypes.byref, ptrs)), handle, kind)
+    return tuple(p.value for p in ptrs)
+
+
+def _set_list_input(export, handle, lead, kind, recs, dtype):
+    """Make `recs` the stage's input list; None goes back to the list of the stage before it."""
+    if recs is None:
+        check(getattr(lib(), export)(handle, *lead, None, 0), handle, kind)
+        return
+    recs = np.ascontiguousarray(recs, dtype=dtype).reshape(-1)
+    keep = recs if recs.size else np.zeros(1, dtype)  # an empty list is still a list: a non-null pointer
+    check(getattr(lib(), export)(handle, *lead, _ptr(keep), recs.size), handle, kind)
+
+
 GDP_STREAM_NULL = 1  # include/gdp.h: selects HIP's default (null) stream
 
 
@@ -177,8 +228,15 @@ class PyramidContext:
 
     def __init__(self, height, width, S=2, octaves=0, batch=1, device=0, row_begin=0, row_end=None,
                  input_format="i32", centre="serial"):
-        L = lib()
+        # everything close() reads exists before the first call that can fail
         self._ctx = ctypes.c_void_p()
+        self._handles = {name: ctypes.c_void_p() for name in _OBJECTS}  # the stage objects, null until first use
+        self._made_from = dict.fromkeys(_OBJECTS)  # the upstream handles each was created from
+        self._capacity = {"orient": (0,), "describe": (0,), "match": (0, 0), "ransac": (0, 0), "warp": ()}  # create's sizes, 0: its default
+        self._records = {"orient": 0, "describe": 0}  # what the object holds per image, known at creation
+        self._train = None  # weak reference to the train context of the match object
+        self._match_readers = weakref.WeakSet()  # the contexts whose match object reads this one's describe object
+        L = lib()
         row_end = height if row_end is None else row_end
         check(L.gdp_create_band(ctypes.byref(self._ctx), int(height), int(width), int(S), int(octaves), int(batch),
                                 int(row_begin), int(row_end), int(device)))
@@ -194,10 +252,6 @@ class PyramidContext:
             self._dims.append((r.value, c.value, f.value))
         self._bound = None  # keeps a caller's device input alive
         self._kp_capacity = 65536  # gdp_set_keypoint_capacity's default
-        self._orient = ctypes.c_void_p()  # the gdp_orient object, created on first use
-        self._orient_capacity = 0         # 0: twice the keypoint capacity at creation
-        self._describe = ctypes.c_void_p()  # the gdp_describe object, created on first use
-        self._describe_capacity = 0         # 0: the orientation object's capacity
         self.input_format = "i32"
         if input_format != "i32":
             self.set_input_format(input_format)
@@ -497,6 +551,68 @@ class PyramidContext:
         check(lib().gdp_checksum(self._ctx, int(b), ctypes.byref(v)), self._ctx)
         return v.value
 
+    # ------------------------------------------------------------------ the stage objects (_OBJECTS)
+    def _readers(self, name):
+        """(context, object) of everything that reads this context's `name` object: the objects made
+        from it here and, for the describe object, the match objects of the contexts that match
+        against this one as their train side."""
+        for reader, entry in _OBJECTS.items():
+            if entry.reads == name:
+                yield self, reader
+        if name == "describe":
+            for other in list(self._match_readers):
+                yield other, "match"
+
+    def _drop(self, name):
+        """Destroy the `name` object and, first, everything that reads it."""
+        for ctx, reader in self._readers(name):
+            ctx._drop(reader)
+        if self._handles[name].value:
+            getattr(lib(), _OBJECTS[name].destroy)(self._handles[name])
+            self._handles[name] = ctypes.c_void_p()
+
+    def _handle(self, name, train=None):
+        """The `name` object, created on first use from the objects it reads (themselves created on
+        first use) and again whenever one of those was.  The match object reads this context's
+        describe object and `train`'s (None: the train side it was last made against, or this
+        context's); it is made again when `train` changes, and holds `train` only weakly."""
+        entry = _OBJECTS[name]
+        if name == "match":
+            kept = self._train() if self._handles["match"].value else None
+            if train is None:
+                train = self if kept is None else kept
+            if train is not kept:
+                self._drop("match")  # before anything of the new train side is created
+        src = ((self._ctx,) if entry.takes_ctx else ()) + ((self._handle(entry.reads),) if entry.reads else ())
+        if name == "match":
+            src += (train._handle("describe"),)
+        made_from = tuple(s.value for s in src)
+        if not self._handles[name].value or self._made_from[name] != made_from:
+            self._drop(name)
+            new = ctypes.c_void_p()
+            check(getattr(lib(), entry.create)(ctypes.byref(new), *src, *self._capacity[name]), None, name)
+            self._handles[name], self._made_from[name] = new, made_from
+            if name == "orient":
+                self._records[name] = self._capacity[name][0] or 2 * self._kp_capacity
+            elif name == "describe":
+                self._records[name] = self._capacity[name][0] or self._records["orient"]
+            elif name == "match":
+                self._train = weakref.ref(train)
+                train._match_readers.add(self)
+        return self._handles[name]
+
+    # the names the stage tests reach the objects by: the handles as they are (null before first use),
+    # and the warp object created on first use
+    _orient, _describe, _match, _ransac = (property(lambda self, name=name: self._handles[name])
+                                           for name in ("orient", "describe", "match", "ransac"))
+
+    def _warp_handle(self):
+        return self._handle("warp")
+
+    def _set_capacity(self, name, capacity):
+        self._drop(name)  # the next use creates it again, of the new size
+        self._capacity[name] = capacity
+
     # ------------------------------------------------------------------ keypoints (extension)
     def set_keypoint_capacity(self, n):
         """Records kept per image by detect_extrema (default 65536); reallocates the buffer."""
@@ -512,26 +628,17 @@ class PyramidContext:
 
     def keypoint_count(self, b=0):
         """Keypoints the last detection found in image b (blocking; may exceed the capacity)."""
-        n = ctypes.c_size_t()
-        check(lib().gdp_keypoint_count(self._ctx, int(b), ctypes.byref(n)), self._ctx)
-        return n.value
+        return _count("gdp_keypoint_count", self._ctx, (int(b),), "ctx")
 
     def keypoints(self, b=0):
         """The stored records of image b as a KEYPOINT_DTYPE array sorted by (octave, scale, row,
         col) (blocking); its `found` attribute is keypoint_count(b)."""
-        out = np.zeros(min(self.keypoint_count(b), self._kp_capacity), KEYPOINT_DTYPE)
-        stored, found = ctypes.c_size_t(), ctypes.c_size_t()
-        check(lib().gdp_download_keypoints(self._ctx, int(b), _ptr(out) if out.size else None, out.size,
-                                           ctypes.byref(stored), ctypes.byref(found)), self._ctx)
-        out = out[:stored.value].view(Keypoints)
-        out.found = found.value
-        return out
+        return _download("gdp_download_keypoints", self._ctx, (int(b),), "ctx", KEYPOINT_DTYPE,
+                         min(self.keypoint_count(b), self._kp_capacity))
 
     def device_keypoints(self, b=0):
         """(device address of image b's records, device address of its uint32 counter)."""
-        recs, count = ctypes.c_void_p(), ctypes.c_void_p()
-        check(lib().gdp_device_keypoints(self._ctx, int(b), ctypes.byref(recs), ctypes.byref(count)), self._ctx)
-        return recs.value, count.value
+        return _device_pointers("gdp_device_keypoints", self._ctx, (int(b),), "ctx")
 
     def refine_keypoints(self, contrast=0.0, edge_ratio=0.0, stream=None):
         """Localise image by image the records of the keypoint list (the last detect_extrema's, or
@@ -543,24 +650,16 @@ class PyramidContext:
 
     def refined_count(self, b=0):
         """Records the last refinement kept in image b (blocking)."""
-        n = ctypes.c_size_t()
-        check(lib().gdp_refined_count(self._ctx, int(b), ctypes.byref(n)), self._ctx)
-        return n.value
+        return _count("gdp_refined_count", self._ctx, (int(b),), "ctx")
 
     def refined_keypoints(self, b=0):
         """The refined records of image b as a REFINED_DTYPE array sorted by (octave, scale, row,
         col) and then by the bits of the other fields (blocking)."""
-        out = np.zeros(self.refined_count(b), REFINED_DTYPE)
-        stored = ctypes.c_size_t()
-        check(lib().gdp_download_refined(self._ctx, int(b), _ptr(out) if out.size else None, out.size,
-                                         ctypes.byref(stored)), self._ctx)
-        return out[:stored.value]
+        return _download("gdp_download_refined", self._ctx, (int(b),), "ctx", REFINED_DTYPE, self.refined_count(b), found=False)
 
     def device_refined(self, b=0):
         """(device address of image b's refined records, device address of its uint32 counter)."""
-        recs, count = ctypes.c_void_p(), ctypes.c_void_p()
-        check(lib().gdp_device_refined(self._ctx, int(b), ctypes.byref(recs), ctypes.byref(count)), self._ctx)
-        return recs.value, count.value
+        return _device_pointers("gdp_device_refined", self._ctx, (int(b),), "ctx")
 
     def upload_keypoints(self, records, b=0):
         """Make `records` (KEYPOINT_DTYPE, or anything numpy converts to it) image b's keypoint
@@ -569,124 +668,64 @@ class PyramidContext:
         check(lib().gdp_upload_keypoints(self._ctx, int(b), _ptr(recs) if recs.size else None, recs.size), self._ctx)
 
     # ------------------------------------------------------------------ orientation (extension)
-    def _orient_handle(self):
-        """The context's gdp_orient object, created on first use (close() destroys it before the
-        context).  It only reads the context: no call below changes the pyramid or the lists."""
-        if not self._orient.value:
-            w = ctypes.c_void_p()
-            check(lib().gdp_orient_create(ctypes.byref(w), self._ctx, int(self._orient_capacity)), None, orient=True)
-            self._orient = w
-            self._orient_records = self._orient_capacity or 2 * self._kp_capacity  # what the object holds per image
-        return self._orient
-
-    def _drop_orient(self):
-        self._drop_describe()  # it reads the orientation object at every launch: it goes first
-        if getattr(self, "_orient", None) and self._orient.value:
-            lib().gdp_orient_destroy(self._orient)
-            self._orient = ctypes.c_void_p()
-
+    # The gdp_orient object only reads the context: no call below changes the pyramid or the lists.
     def set_orient_capacity(self, n):
         """Oriented records kept per image, and the longest list set_orient_input takes (default:
         twice the keypoint capacity when the first orientation call is made).  Drops the earlier
         results and input lists."""
         if int(n) <= 0:
             raise ValueError("the orientation capacity must be > 0")
-        self._drop_orient()
-        self._orient_capacity = int(n)
+        self._set_capacity("orient", (int(n),))
 
     def set_orient_input(self, recs, b=0):
         """Make `recs` (REFINED_DTYPE, or anything numpy converts to it) image b's orientation input
         instead of the context's refined list (blocking; gdp_orient_set_input validates every
         record); None goes back to the refined list."""
-        w = self._orient_handle()
-        if recs is None:
-            check(lib().gdp_orient_set_input(w, int(b), None, 0), w, orient=True)
-            return
-        recs = np.ascontiguousarray(recs, dtype=REFINED_DTYPE).reshape(-1)
-        keep = recs if recs.size else np.zeros(1, REFINED_DTYPE)  # an empty list is still a list: a non-null pointer
-        check(lib().gdp_orient_set_input(w, int(b), _ptr(keep), recs.size), w, orient=True)
+        _set_list_input("gdp_orient_set_input", self._handle("orient"), (int(b),), "orient", recs, REFINED_DTYPE)
 
     def orient_keypoints(self, stream=None):
         """Assign orientations to every image's refined list (the last refine_keypoints', or
         set_orient_input's) on the CURRENT pyramid (gdp_orient_keypoints: the Gaussian level rebuilt
         from levels s..S+2, a 36-bin gradient histogram, one record per peak); asynchronous on
         `stream`, one launch, no host read of the counter."""
-        w = self._orient_handle()
-        check(lib().gdp_orient_keypoints(w, _stream_handle(stream)), w, orient=True)
+        w = self._handle("orient")
+        check(lib().gdp_orient_keypoints(w, _stream_handle(stream)), w, "orient")
 
     def oriented_count(self, b=0):
         """Records the last orientation produced for image b (blocking; may exceed the capacity)."""
-        if not self._orient.value:
-            return 0
-        n = ctypes.c_size_t()
-        check(lib().gdp_oriented_count(self._orient, int(b), ctypes.byref(n)), self._orient, orient=True)
-        return n.value
+        w = self._handles["orient"]
+        return _count("gdp_oriented_count", w, (int(b),), "orient") if w.value else 0
 
     def oriented_keypoints(self, b=0):
         """The stored records of image b as an ORIENTED_DTYPE array sorted by (octave, scale, row,
         col, bin) and then by the records' words (blocking); its `found` attribute is
         oriented_count(b)."""
-        if not self._orient.value:
+        w = self._handles["orient"]
+        if not w.value:
             return np.zeros(0, ORIENTED_DTYPE).view(Keypoints)
-        w = self._orient
-        out = np.zeros(min(self.oriented_count(b), self._orient_records), ORIENTED_DTYPE)
-        stored, found = ctypes.c_size_t(), ctypes.c_size_t()
-        check(lib().gdp_download_oriented(w, int(b), _ptr(out) if out.size else None, out.size, ctypes.byref(stored),
-                                          ctypes.byref(found)), w, orient=True)
-        out = out[:stored.value].view(Keypoints)
-        out.found = found.value
-        return out
+        return _download("gdp_download_oriented", w, (int(b),), "orient", ORIENTED_DTYPE,
+                         min(self.oriented_count(b), self._records["orient"]))
 
     def device_oriented(self, b=0):
         """(device address of image b's oriented records, device address of its uint32 counter)."""
-        w = self._orient_handle()
-        recs, count = ctypes.c_void_p(), ctypes.c_void_p()
-        check(lib().gdp_device_oriented(w, int(b), ctypes.byref(recs), ctypes.byref(count)), w, orient=True)
-        return recs.value, count.value
+        return _device_pointers("gdp_device_oriented", self._handle("orient"), (int(b),), "orient")
 
     # ------------------------------------------------------------------ descriptors (extension)
-    def _describe_handle(self):
-        """The context's gdp_describe object, created on first use from the context and its
-        orientation object (close() destroys it before both).  It only reads them: no call below
-        changes the pyramid or any of the three lists."""
-        if not self._describe.value:
-            src = self._orient_handle()
-            w = ctypes.c_void_p()
-            check(lib().gdp_describe_create(ctypes.byref(w), self._ctx, src, int(self._describe_capacity)), None, describe=True)
-            self._describe = w
-            self._describe_records = self._describe_capacity or self._orient_records  # what the object holds per image
-        return self._describe
-
-    def _drop_describe(self):
-        # every match object that reads this describe object goes first: this context's own, and
-        # those of the contexts that match against this one as their train side
-        self._drop_match()
-        for reader in list(getattr(self, "_match_readers", ())):
-            reader._drop_match()
-        if getattr(self, "_describe", None) and self._describe.value:
-            lib().gdp_describe_destroy(self._describe)
-            self._describe = ctypes.c_void_p()
-
+    # The gdp_describe object only reads the context and its orientation object: no call below changes
+    # the pyramid or any of the three lists.
     def set_describe_capacity(self, n):
         """Described records kept per image, and the longest list set_describe_input takes (default:
         the orientation capacity when the first descriptor call is made).  Drops the earlier results
         and input lists."""
         if int(n) <= 0:
             raise ValueError("the descriptor capacity must be > 0")
-        self._drop_describe()
-        self._describe_capacity = int(n)
+        self._set_capacity("describe", (int(n),))
 
     def set_describe_input(self, recs, b=0):
         """Make `recs` (ORIENTED_DTYPE, or anything numpy converts to it) image b's descriptor input
         instead of the oriented list (blocking; gdp_describe_set_input validates every record, the
         angle's range included); None goes back to the oriented list."""
-        w = self._describe_handle()
-        if recs is None:
-            check(lib().gdp_describe_set_input(w, int(b), None, 0), w, describe=True)
-            return
-        recs = np.ascontiguousarray(recs, dtype=ORIENTED_DTYPE).reshape(-1)
-        keep = recs if recs.size else np.zeros(1, ORIENTED_DTYPE)  # an empty list is still a list: a non-null pointer
-        check(lib().gdp_describe_set_input(w, int(b), _ptr(keep), recs.size), w, describe=True)
+        _set_list_input("gdp_describe_set_input", self._handle("describe"), (int(b),), "describe", recs, ORIENTED_DTYPE)
 
     def describe_keypoints(self, stream=None):
         """Compute the 128-byte SIFT descriptor of every image's oriented list (the last
@@ -694,79 +733,36 @@ class PyramidContext:
         the Gaussian level rebuilt from levels s..S+2, a rotated 4 x 4 x 8 gradient histogram,
         normalised, clipped at 0.2 and quantised); asynchronous on `stream`, one launch, no host read
         of the counter."""
-        w = self._describe_handle()
-        check(lib().gdp_describe_keypoints(w, _stream_handle(stream)), w, describe=True)
+        w = self._handle("describe")
+        check(lib().gdp_describe_keypoints(w, _stream_handle(stream)), w, "describe")
 
     def described_count(self, b=0):
         """Records the last description produced for image b (blocking; may exceed the capacity)."""
-        if not self._describe.value:
-            return 0
-        n = ctypes.c_size_t()
-        check(lib().gdp_described_count(self._describe, int(b), ctypes.byref(n)), self._describe, describe=True)
-        return n.value
+        w = self._handles["describe"]
+        return _count("gdp_described_count", w, (int(b),), "describe") if w.value else 0
 
     def described_keypoints(self, b=0):
         """The stored records of image b as a DESCRIBED_DTYPE array sorted by (octave, scale, row,
         col, bin) and then by the records' words (blocking); its `found` attribute is
         described_count(b)."""
-        if not self._describe.value:
+        w = self._handles["describe"]
+        if not w.value:
             return np.zeros(0, DESCRIBED_DTYPE).view(Keypoints)
-        w = self._describe
-        out = np.zeros(min(self.described_count(b), self._describe_records), DESCRIBED_DTYPE)
-        stored, found = ctypes.c_size_t(), ctypes.c_size_t()
-        check(lib().gdp_download_described(w, int(b), _ptr(out) if out.size else None, out.size, ctypes.byref(stored),
-                                           ctypes.byref(found)), w, describe=True)
-        out = out[:stored.value].view(Keypoints)
-        out.found = found.value
-        return out
+        return _download("gdp_download_described", w, (int(b),), "describe", DESCRIBED_DTYPE,
+                         min(self.described_count(b), self._records["describe"]))
 
     def device_described(self, b=0):
         """(device address of image b's described records, device address of its uint32 counter)."""
-        w = self._describe_handle()
-        recs, count = ctypes.c_void_p(), ctypes.c_void_p()
-        check(lib().gdp_device_described(w, int(b), ctypes.byref(recs), ctypes.byref(count)), w, describe=True)
-        return recs.value, count.value
+        return _device_pointers("gdp_device_described", self._handle("describe"), (int(b),), "describe")
 
     # ------------------------------------------------------------------ descriptor matching (extension)
-    def _match_handle(self, train=None):
-        """The gdp_match object that reads this context's describe object (query side) and
-        `train`'s (None: this context's), created on first use and again when `train` changes.  It
-        only reads the two describe objects and is dropped before either of them."""
-        train = self if train is None else train
-        m = getattr(self, "_match", None)
-        if m is not None and m.value and self._match_train() is train:
-            return m
-        self._drop_match()
-        q, t = self._describe_handle(), train._describe_handle()
-        m = ctypes.c_void_p()
-        qcap, tcap = getattr(self, "_match_capacity", (0, 0))
-        check(lib().gdp_match_create(ctypes.byref(m), q, t, int(qcap), int(tcap)), None, match=True)
-        self._match = m
-        self._match_train = weakref.ref(train)
-        if not hasattr(train, "_match_readers"):
-            train._match_readers = weakref.WeakSet()
-        train._match_readers.add(self)
-        return m
-
-    def _match_current(self):
-        """The match object as last created (its train side kept), or a new one against this context."""
-        m = getattr(self, "_match", None)
-        return self._match_handle(self._match_train() if m is not None and m.value else None)
-
-    def _drop_match(self):
-        self._drop_ransac()  # it reads the match object: it goes first
-        m = getattr(self, "_match", None)
-        if m is not None and m.value:
-            lib().gdp_match_destroy(m)
-            self._match = ctypes.c_void_p()
-
+    # The gdp_match object only reads the two describe objects.
     def set_match_capacity(self, query=0, train=0):
         """Records the match object holds per side (0: that side's descriptor capacity); the query
         capacity is also the most matches kept.  Drops the earlier results and input lists."""
         if int(query) < 0 or int(train) < 0:
             raise ValueError("a match capacity must be >= 0")
-        self._drop_match()
-        self._match_capacity = (int(query), int(train))
+        self._set_capacity("match", (int(query), int(train)))
 
     def match_descriptors(self, train=None, query_image=0, train_image=0, ratio=0.8, max_distance=None, mutual=False, stream=None):
         """Match image `query_image`'s described list of this context against image `train_image`'s
@@ -774,93 +770,52 @@ class PyramidContext:
         (gdp_match_descriptors: exact nearest and second-nearest by squared L2 distance on the i8
         matrix cores, ties to the lowest index; Lowe's ratio test with `ratio` (0: off), a distance
         cap and the mutual test); asynchronous on `stream`, no host read of either counter."""
-        m = self._match_handle(train)
+        m = self._handle("match", self if train is None else train)
         cap = 0xffffffff if max_distance is None else int(max_distance)
         check(lib().gdp_match_descriptors(m, int(query_image), int(train_image), float(ratio), cap, int(bool(mutual)),
-                                          _stream_handle(stream)), m, match=True)
+                                          _stream_handle(stream)), m, "match")
 
     def set_match_input(self, side, recs):
         """Make `recs` (DESCRIBED_DTYPE) the list of `side` (0 query, 1 train) instead of the
         describe object's (blocking; records are not validated: any 176 bytes are a record); None
         goes back to the describe object's list."""
-        m = self._match_current()
-        if recs is None:
-            check(lib().gdp_match_set_input(m, int(side), None, 0), m, match=True)
-            return
-        recs = np.ascontiguousarray(recs, dtype=DESCRIBED_DTYPE).reshape(-1)
-        keep = recs if recs.size else np.zeros(1, DESCRIBED_DTYPE)  # an empty list is still a list: a non-null pointer
-        check(lib().gdp_match_set_input(m, int(side), _ptr(keep), recs.size), m, match=True)
+        _set_list_input("gdp_match_set_input", self._handle("match"), (int(side),), "match", recs, DESCRIBED_DTYPE)
 
     def match_count(self):
         """Records the last match produced (blocking; 0 before any)."""
-        m = getattr(self, "_match", None)
-        if m is None or not m.value:
-            return 0
-        n = ctypes.c_size_t()
-        check(lib().gdp_match_count(m, ctypes.byref(n)), m, match=True)
-        return n.value
+        m = self._handles["match"]
+        return _count("gdp_match_count", m, (), "match") if m.value else 0
 
     def matches(self):
         """The last match's records as a MATCH_DTYPE array sorted by `query` (blocking); its `found`
         attribute is match_count()."""
-        m = getattr(self, "_match", None)
-        if m is None or not m.value:
+        m = self._handles["match"]
+        if not m.value:
             return np.zeros(0, MATCH_DTYPE).view(Keypoints)
-        out = np.zeros(self.match_count(), MATCH_DTYPE)
-        stored, found = ctypes.c_size_t(), ctypes.c_size_t()
-        check(lib().gdp_download_matches(m, _ptr(out) if out.size else None, out.size, ctypes.byref(stored), ctypes.byref(found)),
-              m, match=True)
-        out = out[:stored.value].view(Keypoints)
-        out.found = found.value
-        return out
+        return _download("gdp_download_matches", m, (), "match", MATCH_DTYPE, self.match_count())
 
     def device_matches(self):
         """(device address of the match records, device address of their uint32 counter)."""
-        m = self._match_current()
-        recs, count = ctypes.c_void_p(), ctypes.c_void_p()
-        check(lib().gdp_device_matches(m, ctypes.byref(recs), ctypes.byref(count)), m, match=True)
-        return recs.value, count.value
+        return _device_pointers("gdp_device_matches", self._handle("match"), (), "match")
 
     def match_layout(self):
         """(query capacity, train capacity, chunk granule, train chunks, query chunks) of the match
         object (gdp_match_layout)."""
-        m = self._match_current()
+        m = self._handle("match")
         qc, tc = ctypes.c_size_t(), ctypes.c_size_t()
         unit, tch, qch = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
         check(lib().gdp_match_layout(m, ctypes.byref(qc), ctypes.byref(tc), ctypes.byref(unit), ctypes.byref(tch), ctypes.byref(qch)),
-              m, match=True)
+              m, "match")
         return qc.value, tc.value, unit.value, tch.value, qch.value
 
     # ------------------------------------------------------------------ RANSAC homography (extension)
-    def _ransac_handle(self):
-        """The gdp_ransac object that reads this context's current match object, created on first
-        use and again whenever the match object is (it is dropped before the match object it reads)."""
-        m = self._match_current()
-        r = getattr(self, "_ransac", None)
-        if r is not None and r.value and self._ransac_of == m.value:
-            return r
-        self._drop_ransac()
-        r = ctypes.c_void_p()
-        n, hyp = getattr(self, "_ransac_capacity", (0, 0))
-        check(lib().gdp_ransac_create(ctypes.byref(r), m, int(n), int(hyp)), None, ransac=True)
-        self._ransac, self._ransac_of = r, m.value
-        return r
-
-    def _drop_ransac(self):
-        self._drop_warp()  # it reads the fit object: it goes first
-        r = getattr(self, "_ransac", None)
-        if r is not None and r.value:
-            lib().gdp_ransac_destroy(r)
-            self._ransac = ctypes.c_void_p()
-
     def set_ransac_capacity(self, n=0, max_hypotheses=0):
         """The longest list a fit reads, which is also the most inliers kept (0: the match object's
         query capacity), and the most hypotheses of one fit (0: 4,096; at most 65,536).  Drops the
         earlier results and the input list."""
         if int(n) < 0 or int(max_hypotheses) < 0:
             raise ValueError("a RANSAC capacity must be >= 0")
-        self._drop_ransac()
-        self._ransac_capacity = (int(n), int(max_hypotheses))
+        self._set_capacity("ransac", (int(n), int(max_hypotheses)))
 
     def fit_homography(self, hypotheses=1024, seed=0, threshold=3.0, min_inliers=4, stream=None):
         """Fit a homography to the last match's records (or set_ransac_input's) on the device
@@ -868,153 +823,115 @@ class PyramidContext:
         each scored in float32 against every match with the transfer error `threshold` in pixels,
         the largest count wins, ties to the lowest index); asynchronous on `stream`, no host read of
         the match counter."""
-        r = self._ransac_handle()
+        r = self._handle("ransac")
         check(lib().gdp_fit_homography(r, int(hypotheses), int(seed) & 0xffffffff, float(threshold), int(min_inliers),
-                                       _stream_handle(stream)), r, ransac=True)
+                                       _stream_handle(stream)), r, "ransac")
 
     def set_ransac_input(self, recs):
         """Make `recs` (MATCH_DTYPE) the list a fit reads instead of the match object's (blocking;
         records are not validated: any 32 bytes are a record); None goes back to the match object's."""
-        r = self._ransac_handle()
-        if recs is None:
-            check(lib().gdp_ransac_set_input(r, None, 0), r, ransac=True)
-            return
-        recs = np.ascontiguousarray(recs, dtype=MATCH_DTYPE).reshape(-1)
-        keep = recs if recs.size else np.zeros(1, MATCH_DTYPE)  # an empty list is still a list: a non-null pointer
-        check(lib().gdp_ransac_set_input(r, _ptr(keep), recs.size), r, ransac=True)
+        _set_list_input("gdp_ransac_set_input", self._handle("ransac"), (), "ransac", recs, MATCH_DTYPE)
 
     def homography(self):
         """The last fit's model record (blocking) as a Homography: its `matrix` is the 3 x 3 float32
         array, or None when there is no model (hypothesis = 0xffffffff)."""
-        r = self._ransac_handle()
+        r = self._handle("ransac")
         out = np.zeros(1, HOMOGRAPHY_DTYPE)
-        check(lib().gdp_download_homography(r, _ptr(out)), r, ransac=True)
+        check(lib().gdp_download_homography(r, _ptr(out)), r, "ransac")
         return out[0:1].reshape(()).view(Homography)
 
     def hypotheses(self):
         """Every hypothesis record of the last fit as a HOMOGRAPHY_DTYPE array in index order (blocking)."""
-        r = self._ransac_handle()
+        r = self._handle("ransac")
         _, most, _, _ = self.ransac_layout()
         out = np.zeros(most, HOMOGRAPHY_DTYPE)
         stored = ctypes.c_size_t()
-        check(lib().gdp_download_hypotheses(r, _ptr(out), out.size, ctypes.byref(stored)), r, ransac=True)
+        check(lib().gdp_download_hypotheses(r, _ptr(out), out.size, ctypes.byref(stored)), r, "ransac")
         return out[:stored.value]
 
     def inlier_count(self):
         """Inliers of the last fit (blocking; 0 before any and without a model)."""
-        r = getattr(self, "_ransac", None)
-        if r is None or not r.value:
-            return 0
-        n = ctypes.c_size_t()
-        check(lib().gdp_ransac_count(r, ctypes.byref(n)), r, ransac=True)
-        return n.value
+        r = self._handles["ransac"]
+        return _count("gdp_ransac_count", r, (), "ransac") if r.value else 0
 
     def inliers(self):
         """The last fit's inlier records as a MATCH_DTYPE array sorted by `query` (blocking); its
         `found` attribute is inlier_count()."""
-        r = getattr(self, "_ransac", None)
-        if r is None or not r.value:
+        r = self._handles["ransac"]
+        if not r.value:
             return np.zeros(0, MATCH_DTYPE).view(Keypoints)
-        out = np.zeros(self.inlier_count(), MATCH_DTYPE)
-        stored, found = ctypes.c_size_t(), ctypes.c_size_t()
-        check(lib().gdp_download_inliers(r, _ptr(out) if out.size else None, out.size, ctypes.byref(stored), ctypes.byref(found)),
-              r, ransac=True)
-        out = out[:stored.value].view(Keypoints)
-        out.found = found.value
-        return out
+        return _download("gdp_download_inliers", r, (), "ransac", MATCH_DTYPE, self.inlier_count())
 
     def device_inliers(self):
         """(device address of the inlier records, of their uint32 counter, of the model record)."""
-        r = self._ransac_handle()
-        recs, count, model = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-        check(lib().gdp_device_inliers(r, ctypes.byref(recs), ctypes.byref(count), ctypes.byref(model)), r, ransac=True)
-        return recs.value, count.value, model.value
+        return _device_pointers("gdp_device_inliers", self._handle("ransac"), (), "ransac", n=3)
 
     def ransac_layout(self):
         """(capacity, max hypotheses, match chunk granule, hypotheses per block) of the fit object
         (gdp_ransac_layout)."""
-        r = self._ransac_handle()
+        r = self._handle("ransac")
         cap = ctypes.c_size_t()
         most, mt, ht = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
-        check(lib().gdp_ransac_layout(r, ctypes.byref(cap), ctypes.byref(most), ctypes.byref(mt), ctypes.byref(ht)), r, ransac=True)
+        check(lib().gdp_ransac_layout(r, ctypes.byref(cap), ctypes.byref(most), ctypes.byref(mt), ctypes.byref(ht)), r, "ransac")
         return cap.value, most.value, mt.value, ht.value
 
     # ------------------------------------------------------------------ homography warp (extension)
-    def _warp_handle(self):
-        """The gdp_warp object that reads this context's current fit object, created on first use and
-        again whenever the fit object is (it is dropped before the fit object it reads)."""
-        r = self._ransac_handle()
-        w = getattr(self, "_warp", None)
-        if w is not None and w.value and self._warp_of == r.value:
-            return w
-        self._drop_warp()
-        w = ctypes.c_void_p()
-        check(lib().gdp_warp_create(ctypes.byref(w), r), None, warp=True)
-        self._warp, self._warp_of = w, r.value
-        return w
-
-    def _drop_warp(self):
-        w = getattr(self, "_warp", None)
-        if w is not None and w.value:
-            lib().gdp_warp_destroy(w)
-            self._warp = ctypes.c_void_p()
-
     def warp_image(self, direction="train_to_query", query_image=0, train_image=0, fill=0, stream=None):
         """Resample one input image into the other's frame under the last fit's model record (or
         set_warp_model's matrix) on the device (gdp_warp_image: 'train_to_query' brings image
         `train_image` of the matched train context into image `query_image`'s frame of this context,
         'query_to_train' the other way round under the normalised adjugate; bilinear, ties to even,
         uncovered pixels store `fill`); asynchronous on `stream`, no host read of the model."""
-        w = self._warp_handle()
+        w = self._handle("warp")
         code = WARP_DIRECTIONS.get(direction, direction)
-        check(lib().gdp_warp_image(w, int(code), int(query_image), int(train_image), int(fill), _stream_handle(stream)), w, warp=True)
+        check(lib().gdp_warp_image(w, int(code), int(query_image), int(train_image), int(fill), _stream_handle(stream)), w, "warp")
 
     def set_warp_model(self, h):
         """Make the nine floats of `h` (3 x 3 or flat, row-major, query -> train) the model a warp
         reads instead of the fit's model record (blocking; the floats are not validated); None goes
         back to the fit's."""
-        w = self._warp_handle()
+        w = self._handle("warp")
         if h is None:
-            check(lib().gdp_warp_set_model(w, None), w, warp=True)
+            check(lib().gdp_warp_set_model(w, None), w, "warp")
             return
         h = np.ascontiguousarray(h, dtype=np.float32).reshape(-1)
         if h.size != 9:
             raise ValueError("a warp model is nine floats")
-        check(lib().gdp_warp_set_model(w, _ptr(h)), w, warp=True)
+        check(lib().gdp_warp_set_model(w, _ptr(h)), w, "warp")
 
     def warp_record(self):
         """The last warp's WARP_DTYPE record (blocking; all 0 before any)."""
-        w = self._warp_handle()
+        w = self._handle("warp")
         out = np.zeros(1, WARP_DTYPE)
-        check(lib().gdp_download_warp_record(w, _ptr(out)), w, warp=True)
+        check(lib().gdp_download_warp_record(w, _ptr(out)), w, "warp")
         return out[0]
 
     def device_warped(self):
         """(device address of the warped image, pitch in elements, height, width, 'i32' or 'u8', device
         address of the record): what a context of that size and format binds with bind_device_input."""
-        w = self._warp_handle()
+        w = self._handle("warp")
         pix, rec, pitch = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
         h, wd, fmt = _i(), _i(), _i()
         check(lib().gdp_device_warped(w, ctypes.byref(pix), ctypes.byref(pitch), ctypes.byref(h), ctypes.byref(wd), ctypes.byref(fmt),
-                                      ctypes.byref(rec)), w, warp=True)
+                                      ctypes.byref(rec)), w, "warp")
         return pix.value, pitch.value, h.value, wd.value, "u8" if fmt.value == 1 else "i32", rec.value
 
     def warped(self):
         """The last warp's output as a numpy array of the destination frame's shape in the output
         format, int32 or uint8 (blocking; 0 x 0 before any)."""
-        w = self._warp_handle()
+        w = self._handle("warp")
         _, _, h, wd, fmt, _ = self.device_warped()
         out = np.zeros((h, wd), np.uint8 if fmt == "u8" else np.int32)
         if out.size:
-            check(lib().gdp_download_warped(w, _ptr(out), wd), w, warp=True)
+            check(lib().gdp_download_warped(w, _ptr(out), wd), w, "warp")
         return out
 
     def warp_layout(self):
         """(rows, columns of a wave's tile of the destination frame, consecutive columns per lane)
         (gdp_warp_layout)."""
-        w = self._warp_handle()
+        w = self._handle("warp")
         tr, tc, ppl = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
-        check(lib().gdp_warp_layout(w, ctypes.byref(tr), ctypes.byref(tc), ctypes.byref(ppl)), w, warp=True)
+        check(lib().gdp_warp_layout(w, ctypes.byref(tr), ctypes.byref(tc), ctypes.byref(ppl)), w, "warp")
         return tr.value, tc.value, ppl.value
 
     def device_level_ptr(self, b, o, s):
@@ -1036,8 +953,8 @@ class PyramidContext:
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
-        self._drop_orient()  # the orientation object goes before its context
-        if getattr(self, "_ctx", None) and self._ctx.value:
+        self._drop("orient")  # every stage object goes before its context
+        if self._ctx.value:
             lib().gdp_destroy(self._ctx)
             self._ctx = ctypes.c_void_p()
 
@@ -1097,6 +1014,7 @@ class GaussPyramid:
         self.data = None
         self.initialized = False
         self._defer = False
+        self._ctx = None
         if img is None:
             return
         length = int(len)
@@ -1204,7 +1122,7 @@ class GaussPyramid:
         device) on the device (PyramidContext.warp_image).  Returns (the warped image, int32, and the
         WARP_DTYPE record with `covered` and `sad`).  Neither pyramid nor any list is changed."""
         if other is not None:
-            self._ctx._match_handle(other._ctx)
+            self._ctx._handle("match", other._ctx)
         self._ctx.set_warp_model(model)
         self._ctx.warp_image(direction, 0, 0, fill)
         return self._ctx.warped(), self._ctx.warp_record()
@@ -1296,7 +1214,7 @@ class GaussPyramid:
         return self._ctx.pyramid(0)
 
     def close(self):
-        if getattr(self, "_ctx", None) is not None:
+        if self._ctx is not None:
             self._ctx.close()
 
 

@@ -1,0 +1,418 @@
+"""The lifetime rule of the Python binding's stage objects, on a machine without a GPU and without a
+library call: a plain Python object stands in for libgdp.so and records every call, so the tests see
+which object is created from which, what is destroyed in which order when a capacity changes, a train
+side changes or a context closes (another context's match object included), that nothing is called
+before an object exists, and which *_last_error export an error message comes from.  Only public
+methods of PyramidContext are used."""
+import ctypes
+from collections import namedtuple
+
+import numpy as np
+import pytest
+
+Call = namedtuple("Call", "name handles ints")
+
+GEOMETRY = (16, 16, 2, 2, 1)  # H, W, S, O, B of every stand-in context
+LEVEL_DIMS = (8, 8, 0)
+LAST_ERROR = {"ctx": "gdp_last_error", "orient": "gdp_orient_last_error", "describe": "gdp_describe_last_error",
+              "match": "gdp_match_last_error", "ransac": "gdp_ransac_last_error", "warp": "gdp_warp_last_error"}
+CREATES = ("gdp_create_band", "gdp_orient_create", "gdp_describe_create", "gdp_match_create", "gdp_ransac_create",
+           "gdp_warp_create")
+DESTROYS = ("gdp_destroy", "gdp_orient_destroy", "gdp_describe_destroy", "gdp_match_destroy", "gdp_ransac_destroy",
+            "gdp_warp_destroy")
+
+
+class StandIn:
+    """Plays libgdp: every gdp_* attribute is a function that records Call(name, the handles among its
+    arguments, its integers) and returns 0, or the status set for that export in `status`."""
+
+    def __init__(self):
+        self.calls = []
+        self.status = {}  # export -> the non-zero status it returns
+        self.errors = {export: ("the %s object's text" % kind).encode() for kind, export in LAST_ERROR.items()}
+        self.counts = {}  # count export -> the number it reports
+        self.stored = {}  # download export -> the most records it stores
+        self.created = {}  # create export -> the handles it has handed out, oldest first
+        self.live = set()  # every handle value handed out
+        self._next = 0x1000
+
+    def __getattr__(self, name):
+        if not name.startswith("gdp_"):
+            raise AttributeError(name)
+        return lambda *args: self._call(name, *args)
+
+    def _call(self, name, *args):
+        outs = [a._obj for a in args if type(a).__name__ == "CArgObject"]  # the byref arguments
+        handles = tuple(a.value if a is not None else None for a in args
+                        if a is None or (isinstance(a, ctypes.c_void_p) and a.value in self.live))
+        ints = tuple(a for a in args if isinstance(a, int))
+        if name in self.errors:  # a *_last_error export: queried with the object's handle, or None
+            self.calls.append(Call(name, (args[0].value if args[0] is not None else None,), ()))
+            return self.errors[name]
+        if name == "gdp_status_string":
+            return b"status string %d" % args[0]
+        status = self.status.get(name, 0)
+        if name in CREATES and not status:
+            self._next += 0x10
+            outs[0].value = self._next
+            self.live.add(self._next)
+            self.created.setdefault(name, []).append(self._next)
+            handles = (self._next,) + tuple(h for h in handles if h is not None)
+        self.calls.append(Call(name, handles, ints))
+        if name in DESTROYS:
+            return None
+        if status:
+            return status
+        if name == "gdp_get_geometry":
+            for out, v in zip(outs, GEOMETRY):
+                out.value = v
+        elif name == "gdp_level_dims":
+            for out, v in zip(outs, LEVEL_DIMS):
+                out.value = v
+        elif name.endswith("_count"):
+            outs[0].value = self.counts.get(name, 0)
+        elif name.startswith("gdp_download_") and outs:  # (…, records, capacity, &stored[, &found])
+            outs[0].value = min(ints[-1], self.stored.get(name, ints[-1]))
+            if len(outs) > 1:
+                outs[1].value = self.counts.get(name, 0)
+        return 0
+
+    # what the tests read
+    def made(self, export):
+        """The handles `export` has created, oldest first."""
+        return list(self.created.get(export, ()))
+
+    def destroyed(self, since=0):
+        return [(c.name, c.handles[0]) for c in self.calls[since:] if c.name in DESTROYS]
+
+    def last(self, export):
+        return [c for c in self.calls if c.name == export][-1]
+
+
+@pytest.fixture
+def gdp(pkg, monkeypatch):
+    """(the stand-in, a PyramidContext factory); every context made is closed while the stand-in is
+    still installed, so no handle of its ever reaches the real library."""
+    from sift_parallel_optimization_amd import _lib
+
+    fake = StandIn()
+    monkeypatch.setattr(_lib, "_lib", fake)
+    made = []
+
+    def context():
+        made.append(pkg.PyramidContext(16, 16))
+        return made[-1]
+
+    yield fake, context
+    for ctx in made:
+        ctx.close()
+
+
+def _use_every_stage(ctx, train=None):
+    ctx.orient_keypoints()
+    ctx.describe_keypoints()
+    ctx.match_descriptors(train=train)
+    ctx.fit_homography()
+    ctx.warp_image()
+
+
+def _keypoints():
+    from sift_parallel_optimization_amd.gausspyramid import Keypoints
+
+    return Keypoints
+
+
+def _chain(fake, index=-1):
+    """The handles of the index-th created (orient, describe, match, ransac, warp) objects."""
+    return {name.split("_")[1]: fake.made(name)[index] for name in CREATES[1:]}
+
+
+def test_close_destroys_the_chain_in_order_and_once(gdp):
+    fake, context = gdp
+    ctx = context()
+    _use_every_stage(ctx)
+    c, h = fake.made("gdp_create_band")[0], _chain(fake)
+    assert all(len(fake.made(name)) == 1 for name in CREATES)
+    assert fake.last("gdp_orient_create").handles == (h["orient"], c)
+    assert fake.last("gdp_describe_create").handles == (h["describe"], c, h["orient"])
+    assert fake.last("gdp_match_create").handles == (h["match"], h["describe"], h["describe"])
+    assert fake.last("gdp_ransac_create").handles == (h["ransac"], h["match"])
+    assert fake.last("gdp_warp_create").handles == (h["warp"], h["ransac"])
+    ctx.close()
+    assert fake.destroyed() == [("gdp_warp_destroy", h["warp"]), ("gdp_ransac_destroy", h["ransac"]),
+                                ("gdp_match_destroy", h["match"]), ("gdp_describe_destroy", h["describe"]),
+                                ("gdp_orient_destroy", h["orient"]), ("gdp_destroy", c)]
+    n = len(fake.calls)
+    ctx.close()
+    ctx.__del__()
+    assert len(fake.calls) == n  # nothing is destroyed twice
+
+
+def test_set_orient_capacity_drops_everything_but_the_context(gdp):
+    fake, context = gdp
+    ctx = context()
+    _use_every_stage(ctx)
+    assert fake.last("gdp_orient_create").ints == (0,)
+    h, n = _chain(fake), len(fake.calls)
+    ctx.set_orient_capacity(24)
+    assert fake.destroyed() == [("gdp_%s_destroy" % k, h[k]) for k in ("warp", "ransac", "match", "describe", "orient")]
+    assert len(fake.calls) == n + 5  # and no other call
+    ctx.orient_keypoints()
+    new = fake.made("gdp_orient_create")
+    assert len(new) == 2 and new[1] != h["orient"] and fake.last("gdp_orient_create").ints == (24,)
+    assert fake.last("gdp_orient_keypoints").handles == (new[1], None)
+    ctx.describe_keypoints()
+    made = fake.last("gdp_describe_create")
+    assert made.handles == (made.handles[0], fake.made("gdp_create_band")[0], new[1]) and made.ints == (0,)
+    with pytest.raises(ValueError, match="the orientation capacity must be > 0"):
+        ctx.set_orient_capacity(0)
+
+
+def test_set_describe_capacity_leaves_the_orient_object(gdp):
+    fake, context = gdp
+    ctx = context()
+    _use_every_stage(ctx)
+    h = _chain(fake)
+    ctx.set_describe_capacity(12)
+    assert fake.destroyed() == [("gdp_%s_destroy" % k, h[k]) for k in ("warp", "ransac", "match", "describe")]
+    ctx.describe_keypoints()
+    made = fake.last("gdp_describe_create")
+    assert made.handles[1:] == (fake.made("gdp_create_band")[0], h["orient"]) and made.ints == (12,)
+    assert len(fake.made("gdp_orient_create")) == 1
+    with pytest.raises(ValueError, match="the descriptor capacity must be > 0"):
+        ctx.set_describe_capacity(-1)
+
+
+def test_set_match_capacity_drops_match_and_its_readers_only(gdp):
+    fake, context = gdp
+    ctx = context()
+    _use_every_stage(ctx)
+    h = _chain(fake)
+    ctx.set_match_capacity(3, 5)
+    assert fake.destroyed() == [("gdp_%s_destroy" % k, h[k]) for k in ("warp", "ransac", "match")]
+    ctx.match_descriptors()
+    made = fake.last("gdp_match_create")
+    assert made.handles[1:] == (h["describe"], h["describe"]) and made.ints == (3, 5)
+    assert len(fake.made("gdp_describe_create")) == 1 and len(fake.made("gdp_orient_create")) == 1
+    with pytest.raises(ValueError, match="a match capacity must be >= 0"):
+        ctx.set_match_capacity(-1, 0)
+
+
+def test_set_ransac_capacity_drops_ransac_and_warp_only(gdp):
+    fake, context = gdp
+    ctx = context()
+    _use_every_stage(ctx)
+    h = _chain(fake)
+    ctx.set_ransac_capacity(7, 9)
+    assert fake.destroyed() == [("gdp_%s_destroy" % k, h[k]) for k in ("warp", "ransac")]
+    ctx.warp_image()  # the fit object is made again on the way to the warp object
+    made = fake.last("gdp_ransac_create")
+    assert made.handles[1:] == (h["match"],) and made.ints == (7, 9)
+    assert fake.last("gdp_warp_create").handles[1:] == (made.handles[0],)
+    assert len(fake.made("gdp_match_create")) == 1
+    with pytest.raises(ValueError, match="a RANSAC capacity must be >= 0"):
+        ctx.set_ransac_capacity(0, -1)
+
+
+def test_a_train_context_drops_the_match_objects_of_other_contexts_first(gdp):
+    fake, context = gdp
+    q, t, t2 = context(), context(), context()
+    cq, ct, ct2 = fake.made("gdp_create_band")
+    _use_every_stage(q, train=t)
+    h = _chain(fake)
+    orients, describes = fake.made("gdp_orient_create"), fake.made("gdp_describe_create")
+    assert [c.handles[1] for c in fake.calls if c.name == "gdp_orient_create"] == [cq, ct]  # one per context
+    assert fake.last("gdp_match_create").handles == (h["match"], describes[0], describes[1])
+    t.set_describe_capacity(8)
+    assert fake.destroyed() == [("gdp_warp_destroy", h["warp"]), ("gdp_ransac_destroy", h["ransac"]),
+                                ("gdp_match_destroy", h["match"]), ("gdp_describe_destroy", describes[1])]
+    # the same through close(), which then destroys the train context's own chain
+    _use_every_stage(q, train=t)
+    h2, t_describe = _chain(fake), fake.made("gdp_describe_create")[2]
+    assert fake.last("gdp_describe_create").handles == (t_describe, ct, orients[1])  # made again, of the new size
+    assert fake.last("gdp_describe_create").ints == (8,)
+    assert fake.last("gdp_match_create").handles == (h2["match"], describes[0], t_describe)
+    n = len(fake.calls)
+    t.close()
+    assert fake.destroyed(n) == [("gdp_warp_destroy", h2["warp"]), ("gdp_ransac_destroy", h2["ransac"]),
+                                 ("gdp_match_destroy", h2["match"]), ("gdp_describe_destroy", t_describe),
+                                 ("gdp_orient_destroy", orients[1]), ("gdp_destroy", ct)]
+    assert len(fake.calls) == n + 6
+    # the query context's own orient and describe objects were never touched, and it matches on
+    q.match_descriptors(train=t2)
+    assert fake.last("gdp_match_create").handles[1:] == (describes[0], fake.made("gdp_describe_create")[-1])
+    assert fake.last("gdp_describe_create").handles[1] == ct2
+    assert len([c for c in fake.calls if c.name == "gdp_describe_create" and c.handles[1] == cq]) == 1
+    q.close()
+    assert fake.destroyed()[-4:] == [("gdp_match_destroy", fake.made("gdp_match_create")[-1]),
+                                     ("gdp_describe_destroy", describes[0]), ("gdp_orient_destroy", orients[0]),
+                                     ("gdp_destroy", cq)]
+
+
+def test_changing_the_train_side_drops_the_old_match_fit_and_warp_first(gdp):
+    fake, context = gdp
+    q, t, t2 = context(), context(), context()
+    _use_every_stage(q, train=t)
+    h, n = _chain(fake), len(fake.calls)
+    own = fake.made("gdp_describe_create")[0]
+    q.match_descriptors(train=t)  # the same train side: the same object
+    assert len(fake.calls) == n + 1 and fake.last("gdp_match_descriptors").handles == (h["match"], None)
+    q.match_descriptors(train=t2)
+    dropped = [("gdp_warp_destroy", h["warp"]), ("gdp_ransac_destroy", h["ransac"]), ("gdp_match_destroy", h["match"])]
+    assert [(c.name, c.handles[0]) for c in fake.calls[n + 1:n + 4]] == dropped  # before anything is created
+    assert [c.name for c in fake.calls[n + 4:n + 8]] == ["gdp_orient_create", "gdp_describe_create", "gdp_match_create",
+                                                         "gdp_match_descriptors"]
+    new = fake.last("gdp_match_create")
+    assert new.handles[1:] == (own, fake.made("gdp_describe_create")[2])
+    q.fit_homography()  # keeps the train side it was last matched against
+    assert fake.last("gdp_ransac_create").handles[1:] == (new.handles[0],)
+    q.warp_image()
+    assert fake.last("gdp_warp_create").handles[1:] == (fake.made("gdp_ransac_create")[-1],)
+    assert len(fake.made("gdp_match_create")) == 2 and len(fake.made("gdp_ransac_create")) == 2
+    assert fake.destroyed() == dropped  # t's describe object still stands
+    # once the match object is dropped, the next one is made against this context itself
+    q.set_match_capacity(0, 0)
+    q.fit_homography()
+    assert fake.last("gdp_match_create").handles[1:] == (own, own)
+
+
+def test_no_call_before_the_object_exists(gdp, pkg):
+    fake, context = gdp
+    ctx = context()
+    n = len(fake.calls)
+    assert (ctx.oriented_count(), ctx.described_count(), ctx.match_count(), ctx.inlier_count()) == (0, 0, 0, 0)
+    assert ctx.oriented_count(b=0) == 0 and ctx.described_count(b=0) == 0
+    for got, dtype in ((ctx.oriented_keypoints(), pkg.ORIENTED_DTYPE), (ctx.described_keypoints(b=0), pkg.DESCRIBED_DTYPE),
+                       (ctx.matches(), pkg.MATCH_DTYPE), (ctx.inliers(), pkg.MATCH_DTYPE)):
+        assert type(got) is _keypoints() and got.dtype == dtype and got.shape == (0,) and got.found == 0
+    assert len(fake.calls) == n
+    ctx.close()
+    assert fake.destroyed() == [("gdp_destroy", fake.made("gdp_create_band")[0])]
+
+
+def test_list_downloads_are_sized_trimmed_and_carry_found(gdp, pkg):
+    fake, context = gdp
+    ctx = context()
+    ctx.set_keypoint_capacity(4)
+    ctx.set_orient_capacity(6)
+    _use_every_stage(ctx)
+    c, h = fake.made("gdp_create_band")[0], _chain(fake)
+    cases = (("keypoint_count", "keypoints", "gdp_keypoint_count", "gdp_download_keypoints", c, (0,), 4, pkg.KEYPOINT_DTYPE),
+             ("oriented_count", "oriented_keypoints", "gdp_oriented_count", "gdp_download_oriented", h["orient"], (0,), 6,
+              pkg.ORIENTED_DTYPE),
+             ("described_count", "described_keypoints", "gdp_described_count", "gdp_download_described", h["describe"], (0,), 6,
+              pkg.DESCRIBED_DTYPE),
+             ("match_count", "matches", "gdp_match_count", "gdp_download_matches", h["match"], (), 9, pkg.MATCH_DTYPE),
+             ("inlier_count", "inliers", "gdp_ransac_count", "gdp_download_inliers", h["ransac"], (), 9, pkg.MATCH_DTYPE))
+    for count, download, count_export, download_export, handle, lead, room, dtype in cases:
+        fake.counts[count_export] = fake.counts[download_export] = 9  # more than the capacity holds
+        fake.stored[download_export] = 3
+        assert getattr(ctx, count)() == 9 and fake.last(count_export).handles == (handle,)
+        got = getattr(ctx, download)()
+        assert fake.last(download_export).handles == (handle,) and fake.last(download_export).ints == lead + (room,)
+        assert type(got) is _keypoints() and got.dtype == dtype and got.shape == (3,) and got.found == 9
+    # no capacity set: twice the keypoint capacity, and the orient object's records for the describe object
+    other = context()
+    other.set_keypoint_capacity(4)
+    _use_every_stage(other)
+    assert fake.last("gdp_orient_create").ints == (0,) and fake.last("gdp_describe_create").ints == (0,)
+    assert len(other.oriented_keypoints()) == 3 and fake.last("gdp_download_oriented").ints == (0, 8)
+    assert len(other.described_keypoints()) == 3 and fake.last("gdp_download_described").ints == (0, 8)
+    fake.counts["gdp_refined_count"], fake.stored["gdp_download_refined"] = 5, 2
+    got = ctx.refined_keypoints()
+    assert type(got) is np.ndarray and got.dtype == pkg.REFINED_DTYPE and got.shape == (2,)
+    assert ctx.refined_count() == 5 and fake.last("gdp_download_refined").ints == (0, 5)
+    fake.counts["gdp_match_count"] = 0  # an empty list is downloaded with a null pointer
+    assert ctx.matches().shape == (0,) and fake.last("gdp_download_matches").handles == (h["match"], None)
+    assert fake.last("gdp_download_matches").ints == (0,)
+
+
+def test_set_input_none_empty_and_records(gdp, pkg):
+    fake, context = gdp
+    ctx = context()
+    cases = ((lambda recs: ctx.set_orient_input(recs, 0), "gdp_orient_set_input", "gdp_orient_create", (0,), pkg.REFINED_DTYPE),
+             (lambda recs: ctx.set_describe_input(recs, 0), "gdp_describe_set_input", "gdp_describe_create", (0,),
+              pkg.ORIENTED_DTYPE),
+             (lambda recs: ctx.set_match_input(1, recs), "gdp_match_set_input", "gdp_match_create", (1,), pkg.DESCRIBED_DTYPE),
+             (ctx.set_ransac_input, "gdp_ransac_set_input", "gdp_ransac_create", (), pkg.MATCH_DTYPE))
+    for set_input, export, create, lead, dtype in cases:
+        set_input(None)  # creates the object, as every set_*_input does
+        handle = fake.made(create)[0]
+        assert fake.last(export).handles == (handle, None) and fake.last(export).ints == lead + (0,)
+        set_input(np.zeros(0, dtype))  # an empty list is still a list: a non-null pointer
+        assert fake.last(export).handles == (handle,) and fake.last(export).ints == lead + (0,)
+        set_input(np.zeros(3, dtype)[::2])
+        assert fake.last(export).handles == (handle,) and fake.last(export).ints == lead + (2,)
+        assert len(fake.made(create)) == 1
+    ctx.set_warp_model(None)
+    assert fake.last("gdp_warp_set_model").handles == (fake.made("gdp_warp_create")[0], None)
+    with pytest.raises(ValueError, match="a warp model is nine floats"):
+        ctx.set_warp_model(np.zeros(8))
+
+
+# kind -> (the export that creates the object, a method that uses it, the export behind that method)
+ROUTES = {"ctx": ("gdp_create_band", "build", "gdp_build"),
+          "orient": ("gdp_orient_create", "orient_keypoints", "gdp_orient_keypoints"),
+          "describe": ("gdp_describe_create", "describe_keypoints", "gdp_describe_keypoints"),
+          "match": ("gdp_match_create", "match_descriptors", "gdp_match_descriptors"),
+          "ransac": ("gdp_ransac_create", "fit_homography", "gdp_fit_homography"),
+          "warp": ("gdp_warp_create", "warp_image", "gdp_warp_image")}
+
+
+@pytest.mark.parametrize("kind", sorted(ROUTES))
+def test_an_error_carries_the_text_of_the_object_that_failed(gdp, pkg, kind):
+    fake, context = gdp
+    create, method, export = ROUTES[kind]
+    ctx = context()
+    text = fake.errors[LAST_ERROR[kind]].decode()
+    # a failed call on the object: its last error, asked for with its handle
+    fake.status[export] = 3
+    with pytest.raises(pkg.GdpError) as err:
+        getattr(ctx, method)()
+    handle = fake.made(create)[0]
+    assert str(err.value) == "libgdp status 3: " + text and err.value.status == 3
+    assert fake.calls[-2:] == [fake.last(export), (LAST_ERROR[kind], (handle,), ())] and fake.last(export).handles[0] == handle
+    # no text: the status string
+    fake.errors[LAST_ERROR[kind]] = b""
+    with pytest.raises(pkg.GdpError) as err:
+        getattr(ctx, method)()
+    assert str(err.value) == "libgdp status 3: status string 3" and fake.calls[-1] == (LAST_ERROR[kind], (handle,), ())
+    # a failed create: there is no object, so the text is asked for with None
+    fake.errors[LAST_ERROR[kind]] = text.encode()
+    del fake.status[export]
+    fake.status[create] = 4
+    with pytest.raises(pkg.GdpError) as err:
+        getattr(context(), method)()
+    assert str(err.value) == "libgdp status 4: " + text and err.value.status == 4
+    assert fake.calls[-2:] == [fake.last(create), (LAST_ERROR[kind], (None,), ())]
+
+
+def test_check_takes_the_kind_by_name_and_refuses_an_unknown_one(gdp, pkg):
+    """The one case written after the fold: check()'s selector is a key of LAST_ERROR."""
+    from sift_parallel_optimization_amd._lib import LAST_ERROR as table, check
+
+    fake, _ = gdp
+    assert table == LAST_ERROR and check(0) == 0 and check(0, None, "warp") == 0
+    for kind, export in LAST_ERROR.items():
+        with pytest.raises(pkg.GdpError, match="libgdp status 2: the %s object's text" % kind):
+            check(2, None, kind)
+        assert fake.calls[-1] == (export, (None,), ())
+    n = len(fake.calls)
+    for status in (0, 2):  # at the call, whatever the status
+        with pytest.raises(KeyError):
+            check(status, None, "fit")
+    assert len(fake.calls) == n
+
+
+def test_a_context_whose_init_failed_closes_quietly(gdp, pkg):
+    fake, _ = gdp
+    fake.status["gdp_create_band"] = 4
+    ctx = pkg.PyramidContext.__new__(pkg.PyramidContext)
+    with pytest.raises(pkg.GdpError):
+        ctx.__init__(16, 16)
+    n = len(fake.calls)
+    ctx.close()
+    ctx.__del__()
+    with ctx:
+        pass
+    assert len(fake.calls) == n and fake.destroyed() == []

@@ -105,9 +105,13 @@ def test_python_surface(pkg):
     for cls in (pkg.GaussPyramid, pkg.GaussPyramid_a512omp, pkg.GaussPyramid_a512xp):
         assert callable(cls.FitHomography)
     from sift_parallel_optimization_amd._lib import check
-    import inspect
 
-    assert "ransac" in inspect.signature(check).parameters
+    # a failed create is reported with gdp_ransac_last_error(None), or the status string when that is empty
+    handle = ctypes.c_void_p()
+    with pytest.raises(pkg.GdpError) as err:
+        check(pkg.lib().gdp_ransac_create(ctypes.byref(handle), None, 0, 0), None, "ransac")
+    text = pkg.lib().gdp_ransac_last_error(None) or pkg.lib().gdp_status_string(1)
+    assert err.value.status == 1 and handle.value is None and str(err.value) == "libgdp status 1: " + text.decode()
     rec = np.zeros((), pkg.HOMOGRAPHY_DTYPE)
     rec["hypothesis"] = 0xFFFFFFFF
     from sift_parallel_optimization_amd.gausspyramid import Homography

@@ -113,15 +113,17 @@ def test_python_surface(pkg):
     for cls in (pkg.GaussPyramid, pkg.GaussPyramid_a512omp, pkg.GaussPyramid_a512xp):
         assert callable(cls.WarpImage)
     from sift_parallel_optimization_amd._lib import check
-    import inspect
 
-    assert "warp" in inspect.signature(check).parameters
+    # a failed create is reported with gdp_warp_last_error(None), or the status string when that is empty
+    handle = ctypes.c_void_p()
+    with pytest.raises(pkg.GdpError) as err:
+        check(pkg.lib().gdp_warp_create(ctypes.byref(handle), None), None, "warp")
+    text = pkg.lib().gdp_warp_last_error(None) or pkg.lib().gdp_status_string(1)
+    assert err.value.status == 1 and handle.value is None and str(err.value) == "libgdp status 1: " + text.decode()
     from sift_parallel_optimization_amd.gausspyramid import WARP_DIRECTIONS
 
     assert WARP_DIRECTIONS == {"train_to_query": 0, "query_to_train": 1}
-    # the warp handle goes wherever the fit handle goes
-    src = inspect.getsource(pkg.PyramidContext._drop_ransac)
-    assert "_drop_warp" in src
+    # the warp handle goes wherever the fit handle goes: tests/test_binding_lifetime.py
 
 
 _LAYOUT = """
