@@ -138,6 +138,15 @@ public:
     // the call only.
     std::vector<int32_t> WarpImage(GaussPyramid_hip& other, const float h[9], int direction = GDP_WARP_TRAIN_TO_QUERY,
                                    int32_t fill = 0, gdp_warp_record* record = nullptr, int* rows = nullptr, int* cols = nullptr);
+    // Extension: the last DescribeKeypoints' records of this pyramid matched against those of `other`
+    // again, each query only against the records within `radius` pixels (in x and in y) of its
+    // projection under `h`, on the device (gdp_match_guided in gdp.h has the exact rule: `h` maps this
+    // pyramid's (x, y) to `other`'s, as FitHomography's h[] does; exact nearest and second nearest among
+    // the candidates, the ratio test (0: off) and the cap of MatchDescriptors; `unique` keeps one query
+    // per train record), sorted by `query`.  Neither pyramid nor any list is changed; the object lives
+    // for the call only.
+    std::vector<gdp_match_record> GuidedMatch(GaussPyramid_hip& other, const float h[9], float radius = 3.0f, float ratio = 0.0f,
+                                              uint32_t max_distance = 0xffffffffu, bool unique = true);
     ~GaussPyramid_hip();
     bool initialized;
     bool mirror_host;  // GaussPy two-way: upload before / download after every mutating call (default true)
@@ -539,6 +548,26 @@ inline std::vector<int32_t> GaussPyramid_hip::WarpImage(GaussPyramid_hip& other,
     if (rows) *rows = height;
     if (cols) *cols = width;
     gdp_warp_destroy(w);
+    gdp_ransac_destroy(r);
+    gdp_match_destroy(m);
+    return out;
+}
+
+inline std::vector<gdp_match_record> GaussPyramid_hip::GuidedMatch(GaussPyramid_hip& other, const float h[9], float radius, float ratio,
+                                                                   uint32_t max_distance, bool unique) {
+    const char* const what = "GuidedMatch";
+    ensure_described_(what);
+    other.ensure_described_(what);
+    gdp_match* m = nullptr;  // the two lists are the match object's sides; the fit object only carries the way to them
+    check_<gdp_match>(what, gdp_match_last_error, nullptr, gdp_match_create(&m, describe_, other.describe_, 0, 0));
+    gdp_ransac* r = nullptr;
+    check_<gdp_ransac>(what, gdp_ransac_last_error, nullptr, gdp_ransac_create(&r, m, 1, 1));
+    gdp_guided* g = nullptr;
+    check_<gdp_guided>(what, gdp_guided_last_error, nullptr, gdp_guided_create(&g, r, 0));
+    check_(what, gdp_guided_last_error, g, gdp_guided_set_model(g, h));
+    check_(what, gdp_guided_last_error, g, gdp_match_guided(g, 0, 0, radius, ratio, max_distance, unique ? 1 : 0, nullptr));
+    std::vector<gdp_match_record> out = list_<gdp_match_record>(what, gdp_guided_last_error, g, gdp_guided_count, gdp_download_guided);
+    gdp_guided_destroy(g);
     gdp_ransac_destroy(r);
     gdp_match_destroy(m);
     return out;

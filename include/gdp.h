@@ -833,6 +833,88 @@ int gdp_device_warped(const gdp_warp* w, const void** pixels, size_t* pitch, int
  * tile and the consecutive columns one lane computes; a block is 2 x 2 such tiles. */
 int gdp_warp_layout(const gdp_warp* w, uint32_t* tile_rows, uint32_t* tile_cols, uint32_t* pixels_per_lane);
 
+/* ---- extension: guided matching under the fitted homography on the device ------------------------
+ * What the homography is for on the matching side: with the model known, the partner of a query can
+ * only lie near its projection, so the two lists are matched again inside a window round it — a few
+ * candidates per query instead of the whole train list, and no ratio test needed to reject a wrong
+ * match (no reference counterpart, no parity claim).  It writes nothing of a context, an orientation,
+ * describe, match or ransac object: its state is an object of its own, gdp_guided, created from a
+ * const gdp_ransac.
+ *
+ * The rule.  Inputs: the two lists of gdp_keypoint_described records that the match object behind the
+ * fit reads, Q[0..nq) and T[0..nt), resolved for query_image / train_image exactly as
+ * gdp_match_descriptors resolves them; nine float32 h[0..9), row-major, mapping query (x, y) to train
+ * coordinates (the fit's model record, or the caller's floats); the parameters `radius` r, `ratio`,
+ * `max_distance` and `unique`.
+ *   1 coordinates   (float32.)  Step 7 of the match rule for both lists: (qx, qy) and (tx, ty)
+ *   2 projection    (float32, every operation separately rounded, no contraction, denormals kept.)
+ *                     u = (h0 * qx + h1 * qy) + h2,  v = (h3 * qx + h4 * qy) + h5,  w = (h6 * qx + h7 * qy) + h8.
+ *                   A query with !(w > 0) has NO WINDOW and yields nothing.  sx = u / w, sy = v / w: two
+ *                   IEEE correctly rounded divisions.  The fit's "none" record has h[] = 0, so w = 0 and
+ *                   nothing is output: no flag is read
+ *   3 window        (float32, one rounded operation each.)  x0 = sx - r, x1 = sx + r, y0 = sy - r, y1 = sy + r
+ *   4 candidates    train j is a candidate of query i iff
+ *                     x0 <= tx_j && tx_j <= x1 && y0 <= ty_j && ty_j <= y1:
+ *                   four comparisons and nothing else, so a NaN anywhere fails.  The window is a square
+ *                   on purpose: a predicate made only of comparisons is what a cell search can be
+ *                   exactly conservative for
+ *   5 nearest       dist(i, j) is step 1 of the match rule, an exact integer.  The nearest train of
+ *                   query i minimises (dist(i, j), j) lexicographically over its candidates; `second` is
+ *                   the minimum of dist over its other candidates, 0xffffffff with a single candidate.  A
+ *                   query without a candidate yields no record
+ *   6 ratio, cap    steps 4 and 5 of the match rule unchanged.  A query with a single candidate passes
+ *                   the ratio test: (float)0xffffffff is 2^32
+ *   7 unique        when unique != 0: of the records surviving step 6 that share a `train` index, only
+ *                   the one that minimises (distance, query) lexicographically stays; a loser is absent,
+ *                   it is not matched again.  The output is then one-to-one.  (This stands where the
+ *                   dense matcher has its mutual test, whose swapped search has no exact windowed form.)
+ *   8 addresses     nothing is read from a record except octave, row, col, drow, dcol and desc: any 176
+ *                   bytes are a valid record, and any nine floats a valid h.  A cell index formed from
+ *                   coordinates is clamped into the grid in float before the conversion to integer, and a
+ *                   train with a NaN coordinate is in no cell, because it can be nobody's candidate
+ * At most one gdp_match_record per query, filled as the match rule fills it.  Every quantity is a
+ * function of the two lists, h and the parameters with a total order for ties, so the result is an
+ * exact set, independent of the grid, the order inside a cell and wave timing.  The search bins the
+ * train records into a uniform grid over the train context's W x H frame with cell(x) =
+ * clamp(floorf(x * (1 / c)), 0, G - 1), c a power of two: monotone in x, so the cells cell(x0) ..
+ * cell(x1) hold every candidate whatever the arithmetic rounds.  Out of scope: a circular window, the
+ * mutual test, a fit that reads this list on the device (gdp_ransac_set_input takes it). */
+typedef struct gdp_guided gdp_guided;
+/* A guided-matching object reading one fit object (non-NULL) and, through it, the match object and its
+ * two describe objects: all are only read — looked up at every launch — and must outlive this object:
+ * destroy this one first.  It owns an output buffer of the match object's query capacity (so it cannot
+ * overflow), one uint32 counter, the grid arrays, its per-record scratch and the caller's matrix.
+ * max_cells bounds the grid of a launch (0: 262,144; above 16,777,216 is GDP_ERR_ARG).
+ * gdp_guided_last_error(g) describes g's last failure (g NULL: this thread's last failed create). */
+int gdp_guided_create(gdp_guided** out, const gdp_ransac* src, uint32_t max_cells);
+void gdp_guided_destroy(gdp_guided* g);
+const char* gdp_guided_last_error(const gdp_guided* g);
+/* Make h9[0..9) the model instead of the fit's model record (blocking).  The floats are not validated
+ * (point 8 of the rule).  NULL goes back to the fit's model record. */
+int gdp_guided_set_model(gdp_guided* g, const float* h9);
+/* Match: zeroes the counter and the grid on `stream` (NULL = the QUERY context's own stream), then
+ * launches; asynchronous and stream-ordered.  The two lists' counts and the model record are read on
+ * the device, the host never reads them, so launching this right after gdp_fit_homography on the same
+ * stream is the normal use.  `radius` must be finite and >= 0 and `ratio` 0 (no ratio test) or in
+ * (0, 1]; a NaN, anything else or an image index out of range is GDP_ERR_ARG and nothing changes: the
+ * previous result stays downloadable.  The device order is unspecified. */
+int gdp_match_guided(gdp_guided* g, int query_image, int train_image, float radius, float ratio, uint32_t max_distance,
+                     int unique, void* stream);
+/* Records the last launch produced (blocking; waits for the query context's OWN stream; 0 before any). */
+int gdp_guided_count(gdp_guided* g, size_t* found);
+/* Copy min(found, `capacity`) records to `host` (blocking), sorted ascending by `query`, which is
+ * unique per record.  *stored = records written, *found = gdp_guided_count (either may be NULL). */
+int gdp_download_guided(gdp_guided* g, gdp_match_record* host, size_t capacity, size_t* stored, size_t* found);
+/* Zero-copy view for device consumers: the records (the match object's query capacity of them, the
+ * first *count valid, device order) and the counter. */
+int gdp_device_guided(const gdp_guided* g, const gdp_match_record** records, const uint32_t** count);
+/* The grid of the LAST launch (any output may be NULL): the cell side c — the smallest power of two >=
+ * max(radius / 2, 1), doubled until the train frame takes at most max_cells cells — and the cells per row
+ * and per column, ceil(W / c) x ceil(H / c) (0 and 0 x 0 before any launch); the object's max_cells;
+ * and the lanes that share one query in the search. */
+int gdp_guided_layout(const gdp_guided* g, float* cell_side, uint32_t* cells_x, uint32_t* cells_y, uint32_t* max_cells,
+                      uint32_t* lanes_per_query);
+
 /* ---- output --------------------------------------------------------------------------------
  * The blocking copies below are ordered after work on the context's OWN stream; if a build was
  * launched on another stream, synchronize that stream first. */

@@ -181,6 +181,16 @@ SIGNATURES = {
     "gdp_device_warped": (_c_int, [_p, _pp, ctypes.POINTER(_c_size), ctypes.POINTER(_c_int), ctypes.POINTER(_c_int),
                                    ctypes.POINTER(_c_int), _pp]),
     "gdp_warp_layout": (_c_int, [_p, ctypes.POINTER(_c_u32), ctypes.POINTER(_c_u32), ctypes.POINTER(_c_u32)]),
+    "gdp_guided_create": (_c_int, [_pp, _p, _c_u32]),
+    "gdp_guided_destroy": (None, [_p]),
+    "gdp_guided_last_error": (ctypes.c_char_p, [_p]),
+    "gdp_guided_set_model": (_c_int, [_p, _p]),
+    "gdp_match_guided": (_c_int, [_p, _c_int, _c_int, ctypes.c_float, ctypes.c_float, _c_u32, _c_int, _p]),
+    "gdp_guided_count": (_c_int, [_p, ctypes.POINTER(_c_size)]),
+    "gdp_download_guided": (_c_int, [_p, _p, _c_size, ctypes.POINTER(_c_size), ctypes.POINTER(_c_size)]),
+    "gdp_device_guided": (_c_int, [_p, _pp, _pp]),
+    "gdp_guided_layout": (_c_int, [_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_c_u32), ctypes.POINTER(_c_u32),
+                                   ctypes.POINTER(_c_u32), ctypes.POINTER(_c_u32)]),
     "gdp_checksum": (_c_int, [_p, _c_int, ctypes.POINTER(ctypes.c_uint64)]),
     "gdp_get_taps": (_c_int, [_p, _c_int, _c_int, _c_int, _p]),
     "gdp_set_window_centre": (_c_int, [_p, _c_int]),
@@ -246,13 +256,16 @@ def build_variants():
 # handle kind -> the export that holds its last error text
 LAST_ERROR = {"ctx": "gdp_last_error", "orient": "gdp_orient_last_error", "describe": "gdp_describe_last_error",
               "match": "gdp_match_last_error", "ransac": "gdp_ransac_last_error", "warp": "gdp_warp_last_error"}
+# the same for the objects beside that chain: they read the fit object as the warp object does
+SIDE_LAST_ERROR = {"guided": "gdp_guided_last_error"}
 
 
 def check(status, handle=None, kind="ctx"):
     """Raise GdpError for a non-zero status.  `handle` is the object the failed call was made on, or
-    None for a failed create, and `kind` names what it is (a key of LAST_ERROR; an unknown one is a
-    KeyError): the message is that object's last error text, else gdp_status_string(status)."""
-    last_error = LAST_ERROR[kind]
+    None for a failed create, and `kind` names what it is (a key of LAST_ERROR or SIDE_LAST_ERROR; an
+    unknown one is a KeyError): the message is that object's last error text, else
+    gdp_status_string(status)."""
+    last_error = LAST_ERROR.get(kind) or SIDE_LAST_ERROR[kind]
     if status != GDP_OK:
         L = lib()
         raise GdpError(status, (getattr(L, last_error)(handle) or b"").decode() or L.gdp_status_string(status).decode())

@@ -61,6 +61,7 @@ namespace {
 #include "gdp_match.inc"
 #include "gdp_ransac.inc"
 #include "gdp_warp.inc"
+#include "gdp_guided.inc"
 #include "gdp_util.inc"
 #include "gdp_track.inc"
 
@@ -313,6 +314,31 @@ struct gdp_warp : ErrorState {
     int height = 0, width = 0;             // the last launch's destination frame (0 x 0 before any)
     int format = GDP_INPUT_I32;            // its output format: the source context's input format then
     size_t pitch = 0;                      // its row pitch in elements: the width rounded up to 4
+};
+
+// gdp_guided_create: guided matching's state.  It reads one gdp_ransac object (its model record) and,
+// through it, the match object's two sides, all looked up at every launch and never written; it owns
+// everything it writes.
+struct gdp_guided : ErrorState {
+    const gdp_ransac* src = nullptr;
+    int device = 0;                        // the fit object's device
+    size_t cap[2] = {0, 0};                // the match object's capacities: cap[0] is also the output capacity
+    uint32_t max_cells = 0;                // the most cells a launch's grid may have
+    gdp_match_record* d_out = nullptr;     // [cap[0]]
+    uint32_t* d_count = nullptr;           // the head of one allocation: the counter, three words of padding, then
+    uint32_t* d_hist = nullptr;            // [max_cells] trains per cell, then the scatter's cursors: one memset zeroes both
+    uint32_t* d_start = nullptr;           // [max_cells + 1]: the exclusive scan
+    uint4* d_ordered = nullptr;            // [cap[1]]: (tx, ty, sum d^2, index) in cell order
+    float2* d_xy[2] = {nullptr, nullptr};  // [cap]: the coordinates of both sides
+    uint32_t* d_norm[2] = {nullptr, nullptr};  // [cap]: sum d^2
+    uint32_t* d_tcell = nullptr;           // [cap[1]]: a train's cell, 0xffffffff = none
+    float4* d_win = nullptr;               // [cap[0]]: x0, x1, y0, y1 (NaN: no window)
+    uint4* d_best = nullptr;               // [cap[0]]: the search's (distance, train, second, 0)
+    unsigned long long* d_tmin = nullptr;  // [cap[1]]: min (distance << 32) | query of a train's claimants
+    float* d_h = nullptr;                  // the caller's nine floats
+    bool own_model = false;                // launches read d_h, not the fit's model record
+    float cell_side = 0.0f;                // the last launch's grid (0, 0 x 0 before any)
+    uint32_t cells_x = 0, cells_y = 0;
 };
 
 namespace {
@@ -878,6 +904,7 @@ const gdp_ctx* ctx_of(const gdp_describe* w) { return w->ctx; }
 const gdp_ctx* ctx_of(const gdp_match* m) { return m->side[0]->ctx; }
 const gdp_ctx* ctx_of(const gdp_ransac* r) { return ctx_of(r->src); }
 const gdp_ctx* ctx_of(const gdp_warp* w) { return ctx_of(w->src); }
+const gdp_ctx* ctx_of(const gdp_guided* g) { return ctx_of(g->src); }
 
 // d_in_count of a slot that reads its producer's list, not the caller's
 constexpr uint32_t kNoList = 0xffffffffu;
@@ -3911,6 +3938,180 @@ int gdp_device_warped(const gdp_warp* w, const void** pixels, size_t* pitch, int
     if (width) *width = w->width;
     if (format) *format = w->format;
     if (record) *record = w->d_rec;
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+// ---- extension: guided matching under the fitted homography (gdp_guided.inc) ------------------------
+// No export below takes a mutable context, orientation, describe, match or ransac object: the state is
+// the gdp_guided object's; the model record and the match object's two sides are read.
+
+void gdp_guided_destroy(gdp_guided* g) {
+    if (!g) return;
+    (void)hipSetDevice(g->device);
+    (void)hipDeviceSynchronize();  // a launch on any stream may still read or write the buffers
+    for (void* p : {(void*)g->d_out, (void*)g->d_count, (void*)g->d_start, (void*)g->d_ordered, (void*)g->d_xy[0], (void*)g->d_xy[1],
+                    (void*)g->d_norm[0], (void*)g->d_norm[1], (void*)g->d_tcell, (void*)g->d_win, (void*)g->d_best, (void*)g->d_tmin,
+                    (void*)g->d_h})
+        if (p) (void)hipFree(p);  // d_hist lies inside d_count's allocation
+    delete g;
+}
+
+int gdp_guided_create(gdp_guided** out, const gdp_ransac* src, uint32_t max_cells) try {
+    if (!out || !src) return GDP_ERR_ARG;
+    if (max_cells == 0) max_cells = kGuDefaultCells;
+    if (max_cells > kGuMaxCells) return create_fail(GDP_ERR_ARG, "gdp_guided_create: more than 16,777,216 cells");
+    hipError_t e = hipSetDevice(src->device);
+    if (e != hipSuccess) return create_fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    gdp_guided* g = new gdp_guided;
+    g->src = src;
+    g->device = src->device;
+    g->max_cells = max_cells;
+    for (int s = 0; s < 2; ++s) g->cap[s] = src->src->cap[s];  // at most 2^30 each (gdp_match_create)
+    // no input list of its own and one allocation for the counter and the histogram: finish_create does not
+    // fit, create_failed does
+    auto alloc = [&](auto** p, size_t n) {
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(16, n * sizeof(**p)));
+    };
+    e = alloc_counters(&g->d_count, 4 + (size_t)max_cells, 0);  // the counter, three words of padding, the histogram
+    alloc(&g->d_out, g->cap[0]);
+    alloc(&g->d_start, (size_t)max_cells + 1);
+    alloc(&g->d_ordered, g->cap[1]);
+    for (int s = 0; s < 2; ++s) {
+        alloc(&g->d_xy[s], g->cap[s]);
+        alloc(&g->d_norm[s], g->cap[s]);
+    }
+    alloc(&g->d_tcell, g->cap[1]);
+    alloc(&g->d_win, g->cap[0]);
+    alloc(&g->d_best, g->cap[0]);
+    alloc(&g->d_tmin, g->cap[1]);
+    alloc(&g->d_h, 9);
+    if (e == hipSuccess) e = hipMemset(g->d_h, 0, 9 * sizeof(float));
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // a context's non-blocking stream does not wait for the fills
+    if (e != hipSuccess)
+        return create_failed(g, gdp_guided_destroy, "gdp_guided_create (" + std::to_string(g->cap[0]) + " x " + std::to_string(g->cap[1]) +
+                                                        " records, " + std::to_string(max_cells) + " cells): ", e);
+    g->d_hist = g->d_count + 4;
+    *out = g;
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+const char* gdp_guided_last_error(const gdp_guided* g) { return g ? g->err.c_str() : g_create_error.c_str(); }
+
+int gdp_guided_layout(const gdp_guided* g, float* cell_side, uint32_t* cells_x, uint32_t* cells_y, uint32_t* max_cells,
+                      uint32_t* lanes_per_query) try {
+    if (!g) return GDP_ERR_ARG;
+    if (cell_side) *cell_side = g->cell_side;
+    if (cells_x) *cells_x = g->cells_x;
+    if (cells_y) *cells_y = g->cells_y;
+    if (max_cells) *max_cells = g->max_cells;
+    if (lanes_per_query) *lanes_per_query = kGuLanes;
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+int gdp_guided_set_model(gdp_guided* g, const float* h9) try {
+    if (!g) return GDP_ERR_ARG;
+    if (!h9) {
+        g->own_model = false;
+        return GDP_OK;
+    }
+    const gdp_ctx* c = ctx_of(g);
+    GDP_HIP(g, hipSetDevice(c->device));
+    GDP_SETTLE(g, "gdp_guided_set_model", [&](auto&& f) { f(h9, 9 * sizeof(float)); });
+    // the nine floats are data: a cell index formed from them is clamped into the grid, so nothing is validated
+    GDP_HIP(g, hipMemcpyAsync(g->d_h, track_dma_ptr(h9), 9 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    GDP_HIP(g, hipStreamSynchronize(c->stream));
+    g->own_model = true;
+    return GDP_OK;
+} GDP_ABI_CATCH(g)
+
+// The grid of a launch: the cell side is the smallest power of two >= max(radius / 2, 1), doubled until
+// the W x H train frame takes at most max_cells cells.  A window then spans at most five cells per axis
+// and the cells it touches cover at most (2.5 / 2)^2 of its area; with a side >= radius it is three cells
+// and (3 / 2)^2.  Any grid gives the same result (gdp_guided.inc).
+static void guided_grid(const Geom& train, float radius, uint32_t max_cells, int* log2_side, uint32_t* gx, uint32_t* gy) {
+    int k = 0;
+    while (k < kGuMaxLog2Side && std::ldexp(1.0, k) < 0.5 * (double)radius) ++k;
+    for (;; ++k) {
+        const double side = std::ldexp(1.0, k);
+        const double x = std::max(1.0, std::ceil((double)train.W / side)), y = std::max(1.0, std::ceil((double)train.H / side));
+        if (x * y <= (double)max_cells || k >= kGuMaxLog2Side + 32) {  // one cell long before the second bound
+            *log2_side = k, *gx = (uint32_t)x, *gy = (uint32_t)y;
+            return;
+        }
+    }
+}
+
+int gdp_match_guided(gdp_guided* g, int query_image, int train_image, float radius, float ratio, uint32_t max_distance, int unique,
+                     void* stream) try {
+    if (!g) return GDP_ERR_ARG;
+    if (!(radius >= 0.0f && std::isfinite(radius)))  // a NaN fails the first
+        return g->status(GDP_ERR_ARG, "gdp_match_guided: radius %g is not finite and >= 0", (double)radius);
+    if (!(ratio == 0.0f || (ratio > 0.0f && ratio <= 1.0f)))  // a NaN fails both
+        return g->status(GDP_ERR_ARG, "gdp_match_guided: ratio %g is neither 0 nor in (0, 1]", (double)ratio);
+    const gdp_match* m = g->src->src;
+    const int image[2] = {query_image, train_image};
+    MaSide sd[2];
+    for (int s = 0; s < 2; ++s) {  // the two sides as gdp_match_descriptors resolves them
+        const gdp_describe* d = m->side[s];
+        if (image[s] < 0 || image[s] >= d->ctx->geom.batch)
+            return g->status(GDP_ERR_ARG, "gdp_match_guided: %s image %d of %d", s ? "train" : "query", image[s], d->ctx->geom.batch);
+        sd[s].src = reinterpret_cast<const char*>(d->d_out + (size_t)image[s] * d->capacity);
+        sd[s].src_count = d->d_count + image[s];
+        sd[s].src_cap = (unsigned)std::min<size_t>(std::min(d->capacity, m->cap[s]), 1u << 30);
+        sd[s].own = reinterpret_cast<const char*>(m->d_in[s]);
+        sd[s].own_count = m->d_in_count + s;
+    }
+    int log2_side = 0;
+    uint32_t gx = 1, gy = 1;
+    guided_grid(m->side[1]->ctx->geom, radius, g->max_cells, &log2_side, &gx, &gy);
+    GuidedGrid grid;
+    grid.inv_side = (float)std::ldexp(1.0, -log2_side);
+    grid.xmax = (float)(gx - 1);  // exact: at most 2^24 cells
+    grid.ymax = (float)(gy - 1);
+    grid.gx = gx;
+    grid.cells = gx * gy;
+    GDP_HIP(g, hipSetDevice(g->device));
+    hipStream_t st = ctx_of(g)->pick(stream);
+    const float r2 = ratio * ratio;  // one rounded float32 product
+    const int use_ratio = ratio != 0.0f ? 1 : 0;
+    g->cell_side = (float)std::ldexp(1.0, log2_side);
+    g->cells_x = gx, g->cells_y = gy;
+    // the counter and this grid's histogram: one fill
+    GDP_HIP(g, hipMemsetAsync(g->d_count, 0, (4 + (size_t)grid.cells) * sizeof(uint32_t), st));
+    const size_t longest = std::max<size_t>(1, std::max(g->cap[0], g->cap[1]));
+    const unsigned qblocks = (unsigned)((std::max<size_t>(1, g->cap[0]) + 255) / 256), tblocks = (unsigned)((std::max<size_t>(1, g->cap[1]) + 255) / 256);
+    hipLaunchKernelGGL(k_guided_prepare, dim3((unsigned)((longest + 255) / 256), 2), dim3(256), 0, st, sd[0], sd[1],
+                       reinterpret_cast<const uint32_t*>(g->src->d_model), g->own_model ? g->d_h : static_cast<const float*>(nullptr), radius,
+                       grid, g->d_win, g->d_xy[0], g->d_norm[0], g->d_xy[1], g->d_norm[1], g->d_tcell, g->d_hist, g->d_tmin);
+    hipLaunchKernelGGL(k_guided_scan, dim3(1), dim3(kGuScanThreads), 0, st, g->d_hist, g->d_start, grid.cells);
+    hipLaunchKernelGGL(k_guided_scatter, dim3(tblocks), dim3(256), 0, st, sd[1], g->d_xy[1], g->d_norm[1], g->d_tcell, g->d_hist,
+                       g->d_ordered);
+    constexpr unsigned per_block = kGuBlock / kGuLanes;
+    hipLaunchKernelGGL(k_guided_search, dim3((unsigned)((std::max<size_t>(1, g->cap[0]) + per_block - 1) / per_block)), dim3(kGuBlock), 0, st,
+                       sd[0], sd[1], grid, g->d_win, g->d_norm[0], g->d_start, g->d_ordered, g->d_best);
+    if (unique)
+        hipLaunchKernelGGL(k_guided_claim, dim3(qblocks), dim3(256), 0, st, sd[0], g->d_best, use_ratio, r2, max_distance, g->d_tmin);
+    hipLaunchKernelGGL(k_guided_select, dim3(qblocks), dim3(256), 0, st, sd[0], g->d_best, g->d_xy[0], g->d_xy[1], use_ratio, r2,
+                       max_distance, unique ? 1 : 0, g->d_tmin, reinterpret_cast<uint4*>(g->d_out), g->d_count);
+    GDP_HIP(g, hipGetLastError());
+    return GDP_OK;
+} GDP_ABI_CATCH(g)
+
+int gdp_guided_count(gdp_guided* g, size_t* found) try {
+    if (!g || !found) return g ? g->status(GDP_ERR_ARG, "gdp_guided_count: bad argument") : GDP_ERR_ARG;
+    return read_counter(g, g->d_count, found);
+} GDP_ABI_CATCH(g)
+
+int gdp_download_guided(gdp_guided* g, gdp_match_record* host, size_t capacity, size_t* stored, size_t* found) try {
+    if (!g) return GDP_ERR_ARG;
+    if (!host && capacity) return g->status(GDP_ERR_ARG, "gdp_download_guided: bad argument");
+    return download_sorted(g, "gdp_download_guided", g->d_out, g->d_count, g->cap[0], host, capacity, stored, found);
+} GDP_ABI_CATCH(g)
+
+int gdp_device_guided(const gdp_guided* g, const gdp_match_record** records, const uint32_t** count) try {
+    if (!g) return GDP_ERR_ARG;
+    if (records) *records = g->d_out;
+    if (count) *count = g->d_count;
     return GDP_OK;
 } GDP_ABI_CATCH(nullptr)
 

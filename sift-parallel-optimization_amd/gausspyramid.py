@@ -121,7 +121,7 @@ class Keypoints(np.ndarray):
         self.found = getattr(obj, "found", 0)
 
 
-# The five stage objects a context creates on first use, upstream first, keyed by their kind (the
+# The six stage objects a context creates on first use, upstream first, keyed by their kind (the
 # name check() reports their errors under): the create and destroy exports, whether the create takes
 # the context, and the object it reads — that one is created before it and destroyed after it.
 _Object = namedtuple("_Object", "create destroy takes_ctx reads")
@@ -129,7 +129,8 @@ _OBJECTS = {"orient": _Object("gdp_orient_create", "gdp_orient_destroy", True, N
             "describe": _Object("gdp_describe_create", "gdp_describe_destroy", True, "orient"),
             "match": _Object("gdp_match_create", "gdp_match_destroy", False, "describe"),  # and the train side's
             "ransac": _Object("gdp_ransac_create", "gdp_ransac_destroy", False, "match"),
-            "warp": _Object("gdp_warp_create", "gdp_warp_destroy", False, "ransac")}
+            "warp": _Object("gdp_warp_create", "gdp_warp_destroy", False, "ransac"),
+            "guided": _Object("gdp_guided_create", "gdp_guided_destroy", False, "ransac")}
 
 
 # The list operations every stage has, each once: `export` is called on `handle` (the context or a
@@ -232,7 +233,8 @@ class PyramidContext:
         self._ctx = ctypes.c_void_p()
         self._handles = {name: ctypes.c_void_p() for name in _OBJECTS}  # the stage objects, null until first use
         self._made_from = dict.fromkeys(_OBJECTS)  # the upstream handles each was created from
-        self._capacity = {"orient": (0,), "describe": (0,), "match": (0, 0), "ransac": (0, 0), "warp": ()}  # create's sizes, 0: its default
+        self._capacity = {"orient": (0,), "describe": (0,), "match": (0, 0), "ransac": (0, 0), "warp": (),
+                          "guided": (0,)}  # create's sizes, 0: its default
         self._records = {"orient": 0, "describe": 0}  # what the object holds per image, known at creation
         self._train = None  # weak reference to the train context of the match object
         self._match_readers = weakref.WeakSet()  # the contexts whose match object reads this one's describe object
@@ -875,6 +877,68 @@ class PyramidContext:
         check(lib().gdp_ransac_layout(r, ctypes.byref(cap), ctypes.byref(most), ctypes.byref(mt), ctypes.byref(ht)), r, "ransac")
         return cap.value, most.value, mt.value, ht.value
 
+    # ------------------------------------------------------------------ guided matching (extension)
+    # The gdp_guided object only reads the fit object and, through it, the match object's two sides.
+    def set_guided_capacity(self, max_cells=0):
+        """The most cells the grid of a guided match may have (0: 262,144).  Drops the earlier result
+        and set_guided_model's matrix."""
+        if int(max_cells) < 0:
+            raise ValueError("a cell count must be >= 0")
+        self._set_capacity("guided", (int(max_cells),))
+
+    def guided_match(self, radius, ratio=0.0, max_distance=None, unique=True, query_image=0, train_image=0, stream=None):
+        """Match the two lists of the last match again under the last fit's model record (or
+        set_guided_model's matrix) on the device (gdp_match_guided: every query is projected into the
+        train frame and compared with the train records within `radius` pixels of its projection in
+        x and in y; exact nearest and second-nearest among those, ties to the lowest index; the ratio
+        test (0: off) and the distance cap of match_descriptors; `unique` keeps one query per train
+        record, the nearest, ties to the lowest query); asynchronous on `stream`, no host read of the
+        model or of either counter."""
+        g = self._handle("guided")
+        cap = 0xffffffff if max_distance is None else int(max_distance)
+        check(lib().gdp_match_guided(g, int(query_image), int(train_image), float(radius), float(ratio), cap, int(bool(unique)),
+                                     _stream_handle(stream)), g, "guided")
+
+    def set_guided_model(self, h):
+        """Make the nine floats of `h` (3 x 3 or flat, row-major, query -> train) the model a guided
+        match reads instead of the fit's model record (blocking; the floats are not validated); None
+        goes back to the fit's record."""
+        g = self._handle("guided")
+        if h is None:
+            check(lib().gdp_guided_set_model(g, None), g, "guided")
+            return
+        h = np.ascontiguousarray(h, dtype=np.float32).reshape(-1)
+        if h.size != 9:
+            raise ValueError("a guided model is nine floats")
+        check(lib().gdp_guided_set_model(g, _ptr(h)), g, "guided")
+
+    def guided_count(self):
+        """Records the last guided match produced (blocking; 0 before any)."""
+        g = self._handles["guided"]
+        return _count("gdp_guided_count", g, (), "guided") if g.value else 0
+
+    def guided_matches(self):
+        """The last guided match's records as a MATCH_DTYPE array sorted by `query` (blocking); its
+        `found` attribute is guided_count()."""
+        g = self._handles["guided"]
+        if not g.value:
+            return np.zeros(0, MATCH_DTYPE).view(Keypoints)
+        return _download("gdp_download_guided", g, (), "guided", MATCH_DTYPE, self.guided_count())
+
+    def device_guided(self):
+        """(device address of the guided match records, device address of their uint32 counter)."""
+        return _device_pointers("gdp_device_guided", self._handle("guided"), (), "guided")
+
+    def guided_layout(self):
+        """(cell side, cells per row, cells per column) of the last guided match's grid — 0, 0, 0
+        before any — then (the most cells a grid may have, lanes per query) (gdp_guided_layout)."""
+        g = self._handle("guided")
+        side = ctypes.c_float()
+        gx, gy, most, lanes = (ctypes.c_uint32() for _ in range(4))
+        check(lib().gdp_guided_layout(g, ctypes.byref(side), ctypes.byref(gx), ctypes.byref(gy), ctypes.byref(most), ctypes.byref(lanes)),
+              g, "guided")
+        return side.value, gx.value, gy.value, most.value, lanes.value
+
     # ------------------------------------------------------------------ homography warp (extension)
     def warp_image(self, direction="train_to_query", query_image=0, train_image=0, fill=0, stream=None):
         """Resample one input image into the other's frame under the last fit's model record (or
@@ -1126,6 +1190,19 @@ class GaussPyramid:
         self._ctx.set_warp_model(model)
         self._ctx.warp_image(direction, 0, 0, fill)
         return self._ctx.warped(), self._ctx.warp_record()
+
+    def GuidedMatch(self, other=None, model=None, radius=3.0, ratio=0.0, max_distance=None, unique=True):
+        """Extension: match the last DescribeKeypoints' records of this pyramid against those of
+        `other` (None: the train side of the last MatchDescriptors, or this pyramid) again, each
+        query only against the records within `radius` pixels of its projection under `model` (nine
+        floats mapping this pyramid's (x, y) to `other`'s; None: the last FitHomography's model
+        record, read on the device) on the device (PyramidContext.guided_match).  Returns the
+        MATCH_DTYPE records sorted by `query`.  Neither pyramid nor any list is changed."""
+        if other is not None:
+            self._ctx._handle("match", other._ctx)
+        self._ctx.set_guided_model(model)
+        self._ctx.guided_match(radius, ratio, max_distance, unique)
+        return self._ctx.guided_matches()
 
     def output(self, file=None):
         """:89-104 — print scale 0 of each octave (space separated) and an `==` separator row."""

@@ -278,9 +278,104 @@ static void exercise(int H, int W, int S, int O, int B, int r0, int r1) {
     gdp_destroy(c);
 }
 
+// Guided matching's host layer (gdp_guided_*): the paths that need no handle run on any machine; with a
+// device, the object is made over two lists of the caller's and every export is called, refusals included.
+static void exercise_guided(bool device) {
+    gdp_guided* g = nullptr;
+    size_t n = 0;
+    float side = 0;
+    uint32_t gx = 0, gy = 0, most = 0, lanes = 0;
+    gdp_match_record rec[4];
+    const float eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    EXPECT(gdp_guided_create(&g, nullptr, 0) == GDP_ERR_ARG && g == nullptr);
+    EXPECT(gdp_guided_create(nullptr, nullptr, 0) == GDP_ERR_ARG);
+    gdp_guided_destroy(nullptr);
+    EXPECT(gdp_guided_set_model(nullptr, eye) == GDP_ERR_ARG);
+    EXPECT(gdp_match_guided(nullptr, 0, 0, 3.0f, 0.0f, 0xffffffffu, 1, nullptr) == GDP_ERR_ARG);
+    EXPECT(gdp_guided_count(nullptr, &n) == GDP_ERR_ARG);
+    EXPECT(gdp_download_guided(nullptr, rec, 4, &n, &n) == GDP_ERR_ARG);
+    EXPECT(gdp_device_guided(nullptr, nullptr, nullptr) == GDP_ERR_ARG);
+    EXPECT(gdp_guided_layout(nullptr, &side, &gx, &gy, &most, &lanes) == GDP_ERR_ARG);
+    EXPECT(gdp_guided_last_error(nullptr) != nullptr);
+    if (!device) return;
+    gdp_ctx* c = nullptr;
+    OK(gdp_create(&c, 40, 56, 2, 2, 1, 0));
+    if (!c) return;
+    gdp_orient* o = nullptr;
+    gdp_describe* d = nullptr;
+    gdp_match* m = nullptr;
+    gdp_ransac* r = nullptr;
+    OK(gdp_orient_create(&o, c, 64));
+    OK(gdp_describe_create(&d, c, o, 64));
+    OK(gdp_match_create(&m, d, d, 300, 300));
+    OK(gdp_ransac_create(&r, m, 0, 16));
+    EXPECT(gdp_guided_create(&g, r, (1u << 24) + 1) == GDP_ERR_ARG && g == nullptr);
+    OK(gdp_guided_create(&g, r, 0));
+    if (g) {
+        std::vector<gdp_keypoint_described> list(257);
+        std::memset(list.data(), 0, list.size() * sizeof list[0]);
+        for (size_t i = 0; i < list.size(); ++i) {
+            list[i].dcol = (float)((i * 7) % 56) + 0.25f;
+            list[i].drow = (float)((i * 3) % 40) + 0.5f;
+            for (int k = 0; k < 128; ++k) list[i].desc[k] = (uint8_t)((i * 31 + k * 17) >> 2);
+        }
+        OK(gdp_match_set_input(m, 0, list.data(), 65));
+        OK(gdp_match_set_input(m, 1, list.data(), list.size()));
+        OK(gdp_guided_layout(g, &side, &gx, &gy, &most, &lanes));
+        EXPECT(side == 0.0f && gx == 0 && gy == 0 && most == (1u << 18) && lanes == 8);
+        OK(gdp_guided_count(g, &n));
+        EXPECT(n == 0);
+        OK(gdp_match_guided(g, 0, 0, 3.0f, 0.0f, 0xffffffffu, 1, nullptr));  // the fit's "none" record: nothing
+        OK(gdp_guided_count(g, &n));
+        EXPECT(n == 0);
+        OK(gdp_guided_set_model(g, eye));
+        for (int unique = 0; unique < 2; ++unique) {
+            OK(gdp_match_guided(g, 0, 0, 3.0f, 0.8f, 0xffffffffu, unique, nullptr));
+            std::vector<gdp_match_record> out(65);
+            size_t stored = 0, found = 0;
+            OK(gdp_download_guided(g, out.data(), out.size(), &stored, &found));
+            EXPECT(stored == found && found >= 1 && found <= 65);
+            for (size_t i = 0; i < stored; ++i) EXPECT(out[i].query < 65 && out[i].train < 257 && (i == 0 || out[i - 1].query < out[i].query));
+            OK(gdp_download_guided(g, rec, 2, &stored, &found));  // a buffer shorter than the list: the head of the sorted list
+            EXPECT(stored == (found < 2 ? found : 2) && (stored == 0 || rec[0].query == out[0].query));
+            OK(gdp_download_guided(g, nullptr, 0, &stored, nullptr));
+            EXPECT(gdp_download_guided(g, nullptr, 2, &stored, &found) == GDP_ERR_ARG);
+        }
+        OK(gdp_guided_layout(g, &side, &gx, &gy, nullptr, nullptr));
+        EXPECT(side == 2.0f && gx == 28 && gy == 20);
+        EXPECT(gdp_match_guided(g, 0, 0, -1.0f, 0.0f, 0, 1, nullptr) == GDP_ERR_ARG);
+        EXPECT(gdp_match_guided(g, 0, 0, 3.0f, 1.5f, 0, 1, nullptr) == GDP_ERR_ARG);
+        EXPECT(gdp_match_guided(g, 1, 0, 3.0f, 0.0f, 0, 1, nullptr) == GDP_ERR_ARG);
+        EXPECT(gdp_match_guided(g, 0, -1, 3.0f, 0.0f, 0, 1, nullptr) == GDP_ERR_ARG);
+        EXPECT(std::strlen(gdp_guided_last_error(g)) > 0);
+        EXPECT(gdp_guided_count(g, nullptr) == GDP_ERR_ARG);
+        const gdp_match_record* dev = nullptr;
+        const uint32_t* count = nullptr;
+        OK(gdp_device_guided(g, &dev, &count));
+        EXPECT(dev != nullptr && count != nullptr);
+        OK(gdp_guided_set_model(g, nullptr));
+        OK(gdp_match_guided(g, 0, 0, 1e9f, 0.0f, 0xffffffffu, 0, nullptr));
+        OK(gdp_guided_count(g, &n));
+        EXPECT(n == 0);
+    }
+    OK(gdp_sync(c));
+    gdp_guided_destroy(g);
+    gdp_ransac_destroy(r);
+    gdp_match_destroy(m);
+    gdp_describe_destroy(d);
+    gdp_orient_destroy(o);
+    gdp_destroy(c);
+}
+
 int main() {
     std::setvbuf(stdout, nullptr, _IONBF, 0);
-    EXPECT(gdp_device_count() >= 1);
+    if (gdp_device_count() < 1) {  // no device: what needs no handle still runs under the sanitizers
+        exercise_guided(false);
+        std::printf(failures ? "asan driver (no device, the handle-free paths only): %d failures\n"
+                             : "asan driver (no device, the handle-free paths only): ok\n", failures);
+        return failures ? 1 : 0;
+    }
+    exercise_guided(true);
     exercise(96, 160, 2, 0, 1, 0, 0);
     exercise(100, 37, 3, 0, 2, 0, 0);
     exercise(7, 5, 0, 0, 1, 0, 0);
