@@ -3,7 +3,7 @@
 The product path is the HIP library; there is no CPU fallback.  If libgdp.so is missing or a
 call fails, this module raises GdpError — loudly, never silently computing elsewhere: check() turns a
 status into the error, with the last error text of the object the call was made on (LAST_ERROR names
-the export per kind of handle: the context and the five stage objects).
+the export per kind of handle: the context and the six stage objects).
 
 HIP runtime sharing: the PyTorch-ROCm wheel ships its own libamdhip64.so (soname
 libamdhip64.so.7).  libgdp.so needs `libamdhip64.so.7`; when torch is imported FIRST, the dynamic
@@ -255,17 +255,15 @@ def build_variants():
 
 # handle kind -> the export that holds its last error text
 LAST_ERROR = {"ctx": "gdp_last_error", "orient": "gdp_orient_last_error", "describe": "gdp_describe_last_error",
-              "match": "gdp_match_last_error", "ransac": "gdp_ransac_last_error", "warp": "gdp_warp_last_error"}
-# the same for the objects beside that chain: they read the fit object as the warp object does
-SIDE_LAST_ERROR = {"guided": "gdp_guided_last_error"}
+              "match": "gdp_match_last_error", "ransac": "gdp_ransac_last_error", "warp": "gdp_warp_last_error",
+              "guided": "gdp_guided_last_error"}
 
 
 def check(status, handle=None, kind="ctx"):
     """Raise GdpError for a non-zero status.  `handle` is the object the failed call was made on, or
-    None for a failed create, and `kind` names what it is (a key of LAST_ERROR or SIDE_LAST_ERROR; an
-    unknown one is a KeyError): the message is that object's last error text, else
-    gdp_status_string(status)."""
-    last_error = LAST_ERROR.get(kind) or SIDE_LAST_ERROR[kind]
+    None for a failed create, and `kind` names what it is (a key of LAST_ERROR; an unknown one is a
+    KeyError): the message is that object's last error text, else gdp_status_string(status)."""
+    last_error = LAST_ERROR[kind]
     if status != GDP_OK:
         L = lib()
         raise GdpError(status, (getattr(L, last_error)(handle) or b"").decode() or L.gdp_status_string(status).decode())

@@ -58,6 +58,7 @@ namespace {
 #include "gdp_refine.inc"
 #include "gdp_orient.inc"
 #include "gdp_describe.inc"
+#include "gdp_pairs.inc"
 #include "gdp_match.inc"
 #include "gdp_ransac.inc"
 #include "gdp_warp.inc"
@@ -907,8 +908,8 @@ const gdp_ctx* ctx_of(const gdp_warp* w) { return ctx_of(w->src); }
 const gdp_ctx* ctx_of(const gdp_guided* g) { return ctx_of(g->src); }
 
 // d_in_count of a slot that reads its producer's list, not the caller's
-constexpr uint32_t kNoList = 0xffffffffu;
-static_assert(kOrNoList == kNoList && kDeNoList == kNoList && kMaNoList == kNoList && kRaNoList == kNoList, "one sentinel, filled bytewise (0xff)");
+constexpr uint32_t kNoList = kNone;
+static_assert(kOrNoList == kNoList && kDeNoList == kNoList && kNoList == 0xffffffffu, "one sentinel, filled bytewise (0xff)");
 
 // element i of a device array that may not be allocated yet
 template <class T>
@@ -919,6 +920,18 @@ T* at(T* p, size_t i) {
 int create_fail(int code, const std::string& m) {
     g_create_error = m;
     return code;
+}
+
+// The start of a stage's *_create, after its argument checks: the device the object will live on
+int create_begin(int device) {
+    const hipError_t e = hipSetDevice(device);
+    return e == hipSuccess ? GDP_OK : create_fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+}
+
+// The start of a stage's *_destroy
+void destroy_begin(int device) {
+    (void)hipSetDevice(device);
+    (void)hipDeviceSynchronize();  // a launch on any stream may still read or write the buffers
 }
 
 // A row band does not hold the neighbourhoods of the samples near its edges: "" on a whole-image context
@@ -982,26 +995,29 @@ hipError_t upload_table(float** d_table, const std::vector<float>& table) {
     return e != hipSuccess ? e : hipMemcpy(*d_table, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice);
 }
 
-// A *_create that failed on the device: the object goes, the thread's create error says why
+// The end of every stage's *_create, `e` being what its allocations and fills returned: the object is
+// the caller's, or it goes and the thread's create error says why (`what`: "gdp_x_create (sizes): ")
 template <class W>
-int create_failed(W* w, void (*destroy)(W*), const std::string& what, hipError_t e) {
+int create_end(W** out, W* w, void (*destroy)(W*), const std::string& what, hipError_t e) {
+    if (e == hipSuccess) {
+        *out = w;
+        return GDP_OK;
+    }
     (void)hipGetLastError();
     const std::string m = what + hipGetErrorString(e);
     destroy(w);
     return create_fail(e == hipErrorOutOfMemory ? GDP_ERR_NOMEM : GDP_ERR_HIP, m);
 }
 
-// The end of gdp_orient_create and gdp_describe_create, `e` being what the tables' upload returned:
-// the output list with its counters and the input lists' counters (all on the producer's list)
+// The end of a create whose object has one output list per image and one input list per image (orient,
+// describe, ransac), `e` being what came before: the output list with its counters and the input
+// lists' counters (all on the producer's list)
 template <class W>
 int finish_create(W** out, W* w, void (*destroy)(W*), const char* who, size_t batch, hipError_t e) {
     if (e == hipSuccess) e = alloc_list(&w->d_out, w->capacity * batch, &w->d_count, batch);
     if (e == hipSuccess) e = alloc_counters(&w->d_in_count, batch, 0xff);  // kNoList
-    if (e != hipSuccess)
-        return create_failed(w, destroy, std::string(who) + " (" + std::to_string(w->capacity) + " records x " +
-                                             std::to_string(batch) + " images): ", e);
-    *out = w;
-    return GDP_OK;
+    return create_end(out, w, destroy, std::string(who) + " (" + std::to_string(w->capacity) + " records x " + std::to_string(batch) +
+                                           " images): ", e);
 }
 
 // One counter; 0 while the stage that owns it has not allocated it
@@ -1015,6 +1031,61 @@ int read_counter(H* h, const uint32_t* d_count, size_t* out) {
     GDP_HIP(h, hipMemcpyAsync(&n, d_count, sizeof n, hipMemcpyDeviceToHost, c->stream));
     GDP_HIP(h, hipStreamSynchronize(c->stream));
     *out = n;
+    return GDP_OK;
+}
+
+// `bytes` from the device into the caller's memory after the work on the context's own stream (blocking).
+// read_counter does not go through it: its destination is a local, which no deferred mirror overlaps.
+template <class H>
+int download_blocking(H* h, const char* who, void* host, const void* d_src, size_t bytes) {
+    const gdp_ctx* c = ctx_of(h);
+    GDP_HIP(h, hipSetDevice(c->device));
+    GDP_SETTLE(h, who, [&](auto&& f) { f(host, bytes); });
+    GDP_HIP(h, hipMemcpyAsync(track_dma_ptr(host), d_src, bytes, hipMemcpyDeviceToHost, c->stream));
+    GDP_HIP(h, hipStreamSynchronize(c->stream));
+    return GDP_OK;
+}
+
+// gdp_warp_set_model and gdp_guided_set_model: the caller's nine floats into d_h (blocking), NULL goes
+// back to the fit's model record.  The floats are data: the kernels form no address from them (a cell
+// index formed from them is clamped into the grid), so nothing is validated.
+template <class H>
+int set_own_model(H* h, const char* who, float* d_h, bool* own_model, const float* h9) {
+    if (!h9) {
+        *own_model = false;
+        return GDP_OK;
+    }
+    const gdp_ctx* c = ctx_of(h);
+    GDP_HIP(h, hipSetDevice(c->device));
+    GDP_SETTLE(h, who, [&](auto&& f) { f(h9, 9 * sizeof(float)); });
+    GDP_HIP(h, hipMemcpyAsync(d_h, track_dma_ptr(h9), 9 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    GDP_HIP(h, hipStreamSynchronize(c->stream));
+    *own_model = true;
+    return GDP_OK;
+}
+
+// The ratio of both matching entry points: 0 (no ratio test) or in (0, 1]; a NaN fails both
+template <class H>
+int valid_ratio(H* h, const char* who, float ratio) {
+    if (ratio == 0.0f || (ratio > 0.0f && ratio <= 1.0f)) return GDP_OK;
+    return h->status(GDP_ERR_ARG, "%s: ratio %g is neither 0 nor in (0, 1]", who, (double)ratio);
+}
+
+// The two sides of match object m as a launch of `h` (m itself, or a guided object that reads it)
+// resolves them: the caller's list (gdp_match_set_input), else the chosen image of the side's describe object
+template <class H>
+int match_sides(H* h, const char* who, const gdp_match* m, int query_image, int train_image, MaSide (&sd)[2]) {
+    const int image[2] = {query_image, train_image};
+    for (int s = 0; s < 2; ++s) {
+        const gdp_describe* d = m->side[s];
+        if (image[s] < 0 || image[s] >= d->ctx->geom.batch)
+            return h->status(GDP_ERR_ARG, "%s: %s image %d of %d", who, s ? "train" : "query", image[s], d->ctx->geom.batch);
+        sd[s].src = reinterpret_cast<const char*>(d->d_out + (size_t)image[s] * d->capacity);
+        sd[s].src_count = d->d_count + image[s];
+        sd[s].src_cap = (unsigned)std::min<size_t>(std::min(d->capacity, m->cap[s]), 1u << 30);
+        sd[s].own = reinterpret_cast<const char*>(m->d_in[s]);
+        sd[s].own_count = m->d_in_count + s;
+    }
     return GDP_OK;
 }
 
@@ -3251,8 +3322,7 @@ int gdp_orient_weights(int S, int scale, float* weights, int* radius) try {
 
 void gdp_orient_destroy(gdp_orient* w) {
     if (!w) return;
-    (void)hipSetDevice(w->ctx->device);
-    (void)hipDeviceSynchronize();  // a launch on any stream may still read or write the buffers
+    destroy_begin(w->ctx->device);
     if (w->d_weights) (void)hipFree(w->d_weights);
     if (w->d_out) (void)hipFree(w->d_out);
     if (w->d_count) (void)hipFree(w->d_count);
@@ -3273,8 +3343,7 @@ int gdp_orient_create(gdp_orient** out, const gdp_ctx* c, size_t capacity_per_im
     }
     if (capacity_per_image > (SIZE_MAX / sizeof(gdp_keypoint_oriented)) / batch)
         return create_fail(GDP_ERR_ARG, "gdp_orient_create: capacity does not fit the address space");
-    hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return create_fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (const int rc = create_begin(c->device)) return rc;
     gdp_orient* w = new gdp_orient;
     w->ctx = c;
     w->capacity = capacity_per_image;
@@ -3387,8 +3456,7 @@ int gdp_describe_tables(int S, int scale, float* weights, int* radius, float* co
 
 void gdp_describe_destroy(gdp_describe* w) {
     if (!w) return;
-    (void)hipSetDevice(w->ctx->device);
-    (void)hipDeviceSynchronize();  // a launch on any stream may still read or write the buffers
+    destroy_begin(w->ctx->device);
     if (w->d_weights) (void)hipFree(w->d_weights);
     if (w->d_rot) (void)hipFree(w->d_rot);
     if (w->d_out) (void)hipFree(w->d_out);
@@ -3408,8 +3476,7 @@ int gdp_describe_create(gdp_describe** out, const gdp_ctx* c, const gdp_orient* 
     if (capacity_per_image == 0) capacity_per_image = src ? src->capacity : c->kp_capacity;
     if (capacity_per_image == 0 || capacity_per_image > (SIZE_MAX / sizeof(gdp_keypoint_described)) / batch)
         return create_fail(GDP_ERR_ARG, "gdp_describe_create: capacity does not fit the address space");
-    hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) return create_fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (const int rc = create_begin(c->device)) return rc;
     gdp_describe* w = new gdp_describe;
     w->ctx = c;
     w->src = src;
@@ -3419,7 +3486,7 @@ int gdp_describe_create(gdp_describe** out, const gdp_ctx* c, const gdp_orient* 
     for (int s = 1; s <= g.S; ++s) (void)describe_weights_of(s, table.data() + (size_t)(s - 1) * kDeWeights);
     std::vector<float> rot(2 * (size_t)kDeAngles);
     describe_rotation(rot.data(), rot.data() + kDeAngles);
-    e = upload_table(&w->d_weights, table);
+    hipError_t e = upload_table(&w->d_weights, table);
     if (e == hipSuccess) e = upload_table(&w->d_rot, rot);
     return finish_create(out, w, gdp_describe_destroy, "gdp_describe_create", batch, e);
 } GDP_ABI_CATCH(nullptr)
@@ -3504,8 +3571,7 @@ static unsigned match_chunks(size_t lanes_pad, size_t other_cap) {
 
 void gdp_match_destroy(gdp_match* m) {
     if (!m) return;
-    (void)hipSetDevice(m->device);
-    (void)hipDeviceSynchronize();  // a launch on any stream may still read or write the buffers
+    destroy_begin(m->device);
     if (m->d_out) (void)hipFree(m->d_out);
     if (m->d_count) (void)hipFree(m->d_count);
     if (m->d_in_count) (void)hipFree(m->d_in_count);
@@ -3528,8 +3594,7 @@ int gdp_match_create(gdp_match** out, const gdp_describe* query, const gdp_descr
     // indices and the counter are 32-bit, 0xffffffff is "none", and the grids are sized from these
     if (query_capacity > (1ull << 30) || train_capacity > (1ull << 30))
         return create_fail(GDP_ERR_ARG, "gdp_match_create: a capacity above 2^30 records");
-    hipError_t e = hipSetDevice(query->ctx->device);
-    if (e != hipSuccess) return create_fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (const int rc = create_begin(query->ctx->device)) return rc;
     gdp_match* m = new gdp_match;
     m->side[0] = query;
     m->side[1] = train;
@@ -3539,18 +3604,15 @@ int gdp_match_create(gdp_match** out, const gdp_describe* query, const gdp_descr
     for (int s = 0; s < 2; ++s) m->pad[s] = (size_t)round_up((long long)m->cap[s], kMaTile);
     m->chunks[0] = match_chunks(m->pad[0], m->cap[1]);
     m->chunks[1] = match_chunks(m->pad[1], m->cap[0]);
-    e = alloc_list(&m->d_out, m->cap[0], &m->d_count, 1);
+    hipError_t e = alloc_list(&m->d_out, m->cap[0], &m->d_count, 1);
     if (e == hipSuccess) e = alloc_counters(&m->d_in_count, 2, 0xff);  // kNoList
     for (int s = 0; s < 2 && e == hipSuccess; ++s) {
         e = hipMalloc(reinterpret_cast<void**>(&m->d_norm[s]), m->pad[s] * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_kb[s]), m->pad[s] * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_part[s]), m->chunks[s] * m->pad[s] * sizeof(uint4));
     }
-    if (e != hipSuccess)
-        return create_failed(m, gdp_match_destroy, "gdp_match_create (" + std::to_string(m->cap[0]) + " x " + std::to_string(m->cap[1]) +
-                                                       " records): ", e);
-    *out = m;
-    return GDP_OK;
+    return create_end(out, m, gdp_match_destroy, "gdp_match_create (" + std::to_string(m->cap[0]) + " x " + std::to_string(m->cap[1]) +
+                                                     " records): ", e);
 } GDP_ABI_CATCH(nullptr)
 
 const char* gdp_match_last_error(const gdp_match* m) { return m ? m->err.c_str() : g_create_error.c_str(); }
@@ -3580,20 +3642,9 @@ int gdp_match_set_input(gdp_match* m, int side, const gdp_keypoint_described* ho
 int gdp_match_descriptors(gdp_match* m, int query_image, int train_image, float ratio, uint32_t max_distance, int mutual,
                           void* stream) try {
     if (!m) return GDP_ERR_ARG;
-    if (!(ratio == 0.0f || (ratio > 0.0f && ratio <= 1.0f)))  // a NaN fails both
-        return m->status(GDP_ERR_ARG, "gdp_match_descriptors: ratio %g is neither 0 nor in (0, 1]", (double)ratio);
-    const int image[2] = {query_image, train_image};
     MaSide sd[2];
-    for (int s = 0; s < 2; ++s) {
-        const gdp_describe* d = m->side[s];
-        if (image[s] < 0 || image[s] >= d->ctx->geom.batch)
-            return m->status(GDP_ERR_ARG, "gdp_match_descriptors: %s image %d of %d", s ? "train" : "query", image[s], d->ctx->geom.batch);
-        sd[s].src = reinterpret_cast<const char*>(d->d_out + (size_t)image[s] * d->capacity);
-        sd[s].src_count = d->d_count + image[s];
-        sd[s].src_cap = (unsigned)std::min<size_t>(std::min(d->capacity, m->cap[s]), 1u << 30);
-        sd[s].own = reinterpret_cast<const char*>(m->d_in[s]);
-        sd[s].own_count = m->d_in_count + s;
-    }
+    if (const int rc = valid_ratio(m, "gdp_match_descriptors", ratio)) return rc;
+    if (const int rc = match_sides(m, "gdp_match_descriptors", m, query_image, train_image, sd)) return rc;
     GDP_HIP(m, hipSetDevice(m->device));
     hipStream_t st = m->side[0]->ctx->pick(stream);
     const float r2 = ratio * ratio;  // one rounded float32 product
@@ -3640,8 +3691,7 @@ static_assert(sizeof(gdp_homography) == 64 && sizeof(gdp_match_record) == 32, "f
 
 void gdp_ransac_destroy(gdp_ransac* r) {
     if (!r) return;
-    (void)hipSetDevice(r->device);
-    (void)hipDeviceSynchronize();  // a launch on any stream may still read or write the buffers
+    destroy_begin(r->device);
     if (r->d_hyp) (void)hipFree(r->d_hyp);
     if (r->d_model) (void)hipFree(r->d_model);
     if (r->d_out) (void)hipFree(r->d_out);
@@ -3657,19 +3707,18 @@ int gdp_ransac_create(gdp_ransac** out, const gdp_match* src, size_t capacity, u
     if (max_hypotheses == 0) max_hypotheses = kRaDefaultHypotheses;
     if (capacity > (1ull << 30)) return create_fail(GDP_ERR_ARG, "gdp_ransac_create: a capacity above 2^30 records");
     if (max_hypotheses > kRaMaxHypotheses) return create_fail(GDP_ERR_ARG, "gdp_ransac_create: more than 65,536 hypotheses");
-    hipError_t e = hipSetDevice(src->device);
-    if (e != hipSuccess) return create_fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (const int rc = create_begin(src->device)) return rc;
     gdp_ransac* r = new gdp_ransac;
     r->src = src;
     r->device = src->device;
     r->capacity = capacity;
     r->max_hypotheses = max_hypotheses;
-    e = hipMalloc(reinterpret_cast<void**>(&r->d_hyp), (size_t)max_hypotheses * sizeof(gdp_homography));
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&r->d_hyp), (size_t)max_hypotheses * sizeof(gdp_homography));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&r->d_model), sizeof(gdp_homography));
     if (e == hipSuccess) {  // no model before the first fit
         gdp_homography none{};
-        none.hypothesis = kRaNone;
-        for (uint32_t& s : none.sample) s = kRaNone;
+        none.hypothesis = kNone;
+        for (uint32_t& s : none.sample) s = kNone;
         e = hipMemcpy(r->d_model, &none, sizeof none, hipMemcpyHostToDevice);
     }
     return finish_create(out, r, gdp_ransac_destroy, "gdp_ransac_create", 1, e);
@@ -3736,19 +3785,9 @@ int gdp_ransac_count(gdp_ransac* r, size_t* inliers) try {
     return read_counter(r, r->d_count, inliers);
 } GDP_ABI_CATCH(r)
 
-// `n` records from the device after the work on the context's own stream (blocking)
-static int ransac_records(gdp_ransac* r, const char* who, const gdp_homography* d_recs, gdp_homography* host, size_t n) {
-    const gdp_ctx* c = ctx_of(r);
-    GDP_HIP(r, hipSetDevice(c->device));
-    GDP_SETTLE(r, who, [&](auto&& f) { f(host, n * sizeof(gdp_homography)); });
-    GDP_HIP(r, hipMemcpyAsync(track_dma_ptr(host), d_recs, n * sizeof(gdp_homography), hipMemcpyDeviceToHost, c->stream));
-    GDP_HIP(r, hipStreamSynchronize(c->stream));
-    return GDP_OK;
-}
-
 int gdp_download_homography(gdp_ransac* r, gdp_homography* model) try {
     if (!r || !model) return r ? r->status(GDP_ERR_ARG, "gdp_download_homography: bad argument") : GDP_ERR_ARG;
-    return ransac_records(r, "gdp_download_homography", r->d_model, model, 1);
+    return download_blocking(r, "gdp_download_homography", model, r->d_model, sizeof *model);
 } GDP_ABI_CATCH(r)
 
 int gdp_download_hypotheses(gdp_ransac* r, gdp_homography* host, size_t capacity, size_t* stored) try {
@@ -3757,7 +3796,7 @@ int gdp_download_hypotheses(gdp_ransac* r, gdp_homography* host, size_t capacity
     if (stored) *stored = 0;
     const size_t n = std::min<size_t>(r->hypotheses, capacity);
     if (n == 0) return GDP_OK;
-    const int rc = ransac_records(r, "gdp_download_hypotheses", r->d_hyp, host, n);
+    const int rc = download_blocking(r, "gdp_download_hypotheses", host, r->d_hyp, n * sizeof(gdp_homography));
     if (rc == GDP_OK && stored) *stored = n;
     return rc;
 } GDP_ABI_CATCH(r)
@@ -3788,8 +3827,7 @@ static const gdp_ctx* warp_side(const gdp_warp* w, int side) { return w->src->sr
 
 void gdp_warp_destroy(gdp_warp* w) {
     if (!w) return;
-    (void)hipSetDevice(w->device);
-    (void)hipDeviceSynchronize();  // a launch on any stream may still read or write the buffers
+    destroy_begin(w->device);
     if (w->d_out) (void)hipFree(w->d_out);
     if (w->d_rec) (void)hipFree(w->d_rec);
     if (w->d_h) (void)hipFree(w->d_h);
@@ -3798,27 +3836,22 @@ void gdp_warp_destroy(gdp_warp* w) {
 
 int gdp_warp_create(gdp_warp** out, const gdp_ransac* src) try {
     if (!out || !src) return GDP_ERR_ARG;
-    hipError_t e = hipSetDevice(src->device);
-    if (e != hipSuccess) return create_fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (const int rc = create_begin(src->device)) return rc;
     gdp_warp* w = new gdp_warp;
     w->src = src;
     w->device = src->device;
-    // either context's frame, rows padded to 4 elements, in the wider format.  No list and no counters:
-    // finish_create does not fit, create_failed does
+    // either context's frame, rows padded to 4 elements, in the wider format
     for (int side = 0; side < 2; ++side) {
         const Geom& g = warp_side(w, side)->geom;
         w->out_elements = std::max(w->out_elements, (size_t)g.H * (size_t)round_up(g.W, kWpLanePixels));
     }
-    e = hipMalloc(&w->d_out, std::max<size_t>(16, w->out_elements * sizeof(int32_t)));
+    hipError_t e = hipMalloc(&w->d_out, std::max<size_t>(16, w->out_elements * sizeof(int32_t)));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_rec), sizeof(gdp_warp_record));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->d_h), 9 * sizeof(float));
     if (e == hipSuccess) e = hipMemset(w->d_rec, 0, sizeof(gdp_warp_record));
     if (e == hipSuccess) e = hipMemset(w->d_h, 0, 9 * sizeof(float));
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // a context's non-blocking stream does not wait for the fills
-    if (e != hipSuccess)
-        return create_failed(w, gdp_warp_destroy, "gdp_warp_create (" + std::to_string(w->out_elements) + " pixels): ", e);
-    *out = w;
-    return GDP_OK;
+    return create_end(out, w, gdp_warp_destroy, "gdp_warp_create (" + std::to_string(w->out_elements) + " pixels): ", e);
 } GDP_ABI_CATCH(nullptr)
 
 const char* gdp_warp_last_error(const gdp_warp* w) { return w ? w->err.c_str() : g_create_error.c_str(); }
@@ -3832,19 +3865,7 @@ int gdp_warp_layout(const gdp_warp* w, uint32_t* tile_rows, uint32_t* tile_cols,
 } GDP_ABI_CATCH(nullptr)
 
 int gdp_warp_set_model(gdp_warp* w, const float* h9) try {
-    if (!w) return GDP_ERR_ARG;
-    if (!h9) {
-        w->own_model = false;
-        return GDP_OK;
-    }
-    const gdp_ctx* c = ctx_of(w);
-    GDP_HIP(w, hipSetDevice(c->device));
-    GDP_SETTLE(w, "gdp_warp_set_model", [&](auto&& f) { f(h9, 9 * sizeof(float)); });
-    // the nine floats are data: the kernels form no address from them, so nothing is validated
-    GDP_HIP(w, hipMemcpyAsync(w->d_h, track_dma_ptr(h9), 9 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    GDP_HIP(w, hipStreamSynchronize(c->stream));
-    w->own_model = true;
-    return GDP_OK;
+    return w ? set_own_model(w, "gdp_warp_set_model", w->d_h, &w->own_model, h9) : GDP_ERR_ARG;
 } GDP_ABI_CATCH(w)
 
 int gdp_warp_image(gdp_warp* w, int direction, int query_image, int train_image, int32_t fill, void* stream) try {
@@ -3905,12 +3926,7 @@ int gdp_warp_image(gdp_warp* w, int direction, int query_image, int train_image,
 
 int gdp_download_warp_record(gdp_warp* w, gdp_warp_record* rec) try {
     if (!w || !rec) return w ? w->status(GDP_ERR_ARG, "gdp_download_warp_record: bad argument") : GDP_ERR_ARG;
-    const gdp_ctx* c = ctx_of(w);
-    GDP_HIP(w, hipSetDevice(c->device));
-    GDP_SETTLE(w, "gdp_download_warp_record", [&](auto&& f) { f(rec, sizeof *rec); });
-    GDP_HIP(w, hipMemcpyAsync(track_dma_ptr(rec), w->d_rec, sizeof *rec, hipMemcpyDeviceToHost, c->stream));
-    GDP_HIP(w, hipStreamSynchronize(c->stream));
-    return GDP_OK;
+    return download_blocking(w, "gdp_download_warp_record", rec, w->d_rec, sizeof *rec);
 } GDP_ABI_CATCH(w)
 
 int gdp_download_warped(gdp_warp* w, void* host, size_t pitch_elements) try {
@@ -3947,8 +3963,7 @@ int gdp_device_warped(const gdp_warp* w, const void** pixels, size_t* pitch, int
 
 void gdp_guided_destroy(gdp_guided* g) {
     if (!g) return;
-    (void)hipSetDevice(g->device);
-    (void)hipDeviceSynchronize();  // a launch on any stream may still read or write the buffers
+    destroy_begin(g->device);
     for (void* p : {(void*)g->d_out, (void*)g->d_count, (void*)g->d_start, (void*)g->d_ordered, (void*)g->d_xy[0], (void*)g->d_xy[1],
                     (void*)g->d_norm[0], (void*)g->d_norm[1], (void*)g->d_tcell, (void*)g->d_win, (void*)g->d_best, (void*)g->d_tmin,
                     (void*)g->d_h})
@@ -3960,19 +3975,18 @@ int gdp_guided_create(gdp_guided** out, const gdp_ransac* src, uint32_t max_cell
     if (!out || !src) return GDP_ERR_ARG;
     if (max_cells == 0) max_cells = kGuDefaultCells;
     if (max_cells > kGuMaxCells) return create_fail(GDP_ERR_ARG, "gdp_guided_create: more than 16,777,216 cells");
-    hipError_t e = hipSetDevice(src->device);
-    if (e != hipSuccess) return create_fail(GDP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (const int rc = create_begin(src->device)) return rc;
     gdp_guided* g = new gdp_guided;
     g->src = src;
     g->device = src->device;
     g->max_cells = max_cells;
     for (int s = 0; s < 2; ++s) g->cap[s] = src->src->cap[s];  // at most 2^30 each (gdp_match_create)
-    // no input list of its own and one allocation for the counter and the histogram: finish_create does not
-    // fit, create_failed does
+    // no input list of its own, and one allocation for the counter, three words of padding and the histogram
+    hipError_t e = alloc_counters(&g->d_count, 4 + (size_t)max_cells, 0);
+    if (e == hipSuccess) g->d_hist = g->d_count + 4;
     auto alloc = [&](auto** p, size_t n) {
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(16, n * sizeof(**p)));
     };
-    e = alloc_counters(&g->d_count, 4 + (size_t)max_cells, 0);  // the counter, three words of padding, the histogram
     alloc(&g->d_out, g->cap[0]);
     alloc(&g->d_start, (size_t)max_cells + 1);
     alloc(&g->d_ordered, g->cap[1]);
@@ -3987,12 +4001,8 @@ int gdp_guided_create(gdp_guided** out, const gdp_ransac* src, uint32_t max_cell
     alloc(&g->d_h, 9);
     if (e == hipSuccess) e = hipMemset(g->d_h, 0, 9 * sizeof(float));
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // a context's non-blocking stream does not wait for the fills
-    if (e != hipSuccess)
-        return create_failed(g, gdp_guided_destroy, "gdp_guided_create (" + std::to_string(g->cap[0]) + " x " + std::to_string(g->cap[1]) +
-                                                        " records, " + std::to_string(max_cells) + " cells): ", e);
-    g->d_hist = g->d_count + 4;
-    *out = g;
-    return GDP_OK;
+    return create_end(out, g, gdp_guided_destroy, "gdp_guided_create (" + std::to_string(g->cap[0]) + " x " + std::to_string(g->cap[1]) +
+                                                      " records, " + std::to_string(max_cells) + " cells): ", e);
 } GDP_ABI_CATCH(nullptr)
 
 const char* gdp_guided_last_error(const gdp_guided* g) { return g ? g->err.c_str() : g_create_error.c_str(); }
@@ -4009,19 +4019,7 @@ int gdp_guided_layout(const gdp_guided* g, float* cell_side, uint32_t* cells_x, 
 } GDP_ABI_CATCH(nullptr)
 
 int gdp_guided_set_model(gdp_guided* g, const float* h9) try {
-    if (!g) return GDP_ERR_ARG;
-    if (!h9) {
-        g->own_model = false;
-        return GDP_OK;
-    }
-    const gdp_ctx* c = ctx_of(g);
-    GDP_HIP(g, hipSetDevice(c->device));
-    GDP_SETTLE(g, "gdp_guided_set_model", [&](auto&& f) { f(h9, 9 * sizeof(float)); });
-    // the nine floats are data: a cell index formed from them is clamped into the grid, so nothing is validated
-    GDP_HIP(g, hipMemcpyAsync(g->d_h, track_dma_ptr(h9), 9 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    GDP_HIP(g, hipStreamSynchronize(c->stream));
-    g->own_model = true;
-    return GDP_OK;
+    return g ? set_own_model(g, "gdp_guided_set_model", g->d_h, &g->own_model, h9) : GDP_ERR_ARG;
 } GDP_ABI_CATCH(g)
 
 // The grid of a launch: the cell side is the smallest power of two >= max(radius / 2, 1), doubled until
@@ -4046,21 +4044,10 @@ int gdp_match_guided(gdp_guided* g, int query_image, int train_image, float radi
     if (!g) return GDP_ERR_ARG;
     if (!(radius >= 0.0f && std::isfinite(radius)))  // a NaN fails the first
         return g->status(GDP_ERR_ARG, "gdp_match_guided: radius %g is not finite and >= 0", (double)radius);
-    if (!(ratio == 0.0f || (ratio > 0.0f && ratio <= 1.0f)))  // a NaN fails both
-        return g->status(GDP_ERR_ARG, "gdp_match_guided: ratio %g is neither 0 nor in (0, 1]", (double)ratio);
     const gdp_match* m = g->src->src;
-    const int image[2] = {query_image, train_image};
     MaSide sd[2];
-    for (int s = 0; s < 2; ++s) {  // the two sides as gdp_match_descriptors resolves them
-        const gdp_describe* d = m->side[s];
-        if (image[s] < 0 || image[s] >= d->ctx->geom.batch)
-            return g->status(GDP_ERR_ARG, "gdp_match_guided: %s image %d of %d", s ? "train" : "query", image[s], d->ctx->geom.batch);
-        sd[s].src = reinterpret_cast<const char*>(d->d_out + (size_t)image[s] * d->capacity);
-        sd[s].src_count = d->d_count + image[s];
-        sd[s].src_cap = (unsigned)std::min<size_t>(std::min(d->capacity, m->cap[s]), 1u << 30);
-        sd[s].own = reinterpret_cast<const char*>(m->d_in[s]);
-        sd[s].own_count = m->d_in_count + s;
-    }
+    if (const int rc = valid_ratio(g, "gdp_match_guided", ratio)) return rc;
+    if (const int rc = match_sides(g, "gdp_match_guided", m, query_image, train_image, sd)) return rc;
     int log2_side = 0;
     uint32_t gx = 1, gy = 1;
     guided_grid(m->side[1]->ctx->geom, radius, g->max_cells, &log2_side, &gx, &gy);

@@ -32,8 +32,6 @@ constexpr int kGuScanThreads = 1024;          // k_guided_scan's one block
 constexpr uint32_t kGuDefaultCells = 1u << 18;  // cells of the grid at most, unless the caller says otherwise
 constexpr uint32_t kGuMaxCells = 1u << 24;
 constexpr int kGuMaxLog2Side = 64;            // the cell side is 2^0 .. 2^64
-constexpr uint32_t kGuNone = 0xffffffffu;     // no candidate: a distance, an index or a cell
-static_assert(kGuNone == kMaNone && kGuNone == kRaNone, "one sentinel");
 
 struct GuidedGrid {
     float inv_side;      // 1 / c, a power of two
@@ -41,15 +39,7 @@ struct GuidedGrid {
     unsigned gx, cells;  // cells per row; gx * gy
 };
 
-// step 7 of the match rule
-__device__ __forceinline__ void gu_coordinates(const char* rec, float& x, float& y) {
-    const uint4* p = reinterpret_cast<const uint4*>(rec);
-    const uint4 w0 = p[0], w1 = p[1];  // octave | scale | kind, row, col, value;  dscale, drow, dcol, interp
-    const float sc = (float)(1u << (w0.x & 31u));
-    x = ((float)(int)w0.z + __uint_as_float(w1.z)) * sc;
-    y = ((float)(int)w0.y + __uint_as_float(w1.y)) * sc;
-}
-
+// sum d^2 on the unsigned bytes (k_match_norm's is of the bytes shifted by 128, for the MFMA path)
 __device__ __forceinline__ uint32_t gu_norm(const char* rec) {
     const uint4* d = reinterpret_cast<const uint4*>(rec + kMaDesc);
     uint32_t sum = 0;
@@ -81,16 +71,14 @@ __global__ __launch_bounds__(256) void k_guided_prepare(MaSide Q, MaSide T, cons
     const unsigned k = blockIdx.x * 256u + threadIdx.x;
     const char* recs;
     if (blockIdx.y == 0) {
-        const unsigned nq = ma_resolve(Q, recs);
+        const unsigned nq = list_resolve(Q, recs);
         if (k >= nq) return;
         const char* rec = recs + (size_t)k * kMaRecord;
         float h[9];
-        for (int e = 0; e < 9; ++e) h[e] = own ? own[e] : __uint_as_float(model[e]);
-        float qx, qy;
-        gu_coordinates(rec, qx, qy);
-        const float u = (h[0] * qx + h[1] * qy) + h[2];
-        const float v = (h[3] * qx + h[4] * qy) + h[5];
-        const float w = (h[6] * qx + h[7] * qy) + h[8];
+        load_model(model, own, h);
+        float qx, qy, u, v, w;
+        record_xy(rec, qx, qy);
+        project(h, qx, qy, u, v, w);
         const float nan = __uint_as_float(0x7fc00000u);
         float4 box = make_float4(nan, nan, nan, nan);  // no window: every comparison fails
         if (w > 0.0f) {
@@ -102,15 +90,15 @@ __global__ __launch_bounds__(256) void k_guided_prepare(MaSide Q, MaSide T, cons
         qnorm[k] = gu_norm(rec);
         return;
     }
-    const unsigned nt = ma_resolve(T, recs);
+    const unsigned nt = list_resolve(T, recs);
     if (k >= nt) return;
     const char* rec = recs + (size_t)k * kMaRecord;
     float tx, ty;
-    gu_coordinates(rec, tx, ty);
+    record_xy(rec, tx, ty);
     txy[k] = make_float2(tx, ty);
     tnorm[k] = gu_norm(rec);
     tmin[k] = ~0ull;
-    uint32_t cell = kGuNone;  // a NaN coordinate is nobody's candidate: in no cell
+    uint32_t cell = kNone;  // a NaN coordinate is nobody's candidate: in no cell
     if (tx == tx && ty == ty) {
         cell = gu_cell(ty, g.inv_side, g.ymax) * g.gx + gu_cell(tx, g.inv_side, g.xmax);
         atomicAdd(hist + cell, 1u);
@@ -151,30 +139,30 @@ __global__ __launch_bounds__(256) void k_guided_scatter(MaSide T, const float2* 
                                                         const uint32_t* __restrict__ tcell, uint32_t* __restrict__ cursor,
                                                         uint4* __restrict__ ordered) {
     const char* recs;
-    const unsigned nt = ma_resolve(T, recs);
+    const unsigned nt = list_resolve(T, recs);
     const unsigned j = blockIdx.x * 256u + threadIdx.x;
     if (j >= nt) return;
     const uint32_t cell = tcell[j];
-    if (cell == kGuNone) return;
+    if (cell == kNone) return;
     const uint32_t at = atomicAdd(cursor + cell, 1u);  // below start[cell + 1] <= nt: the histogram counted this train
     const float2 p = txy[j];
     ordered[at] = make_uint4(__float_as_uint(p.x), __float_as_uint(p.y), tnorm[j], j);
 }
 
-// Query blockIdx.x * 32 + threadIdx.x / 8.  best[i] = (distance, train, second, 0), all kGuNone without a candidate.
+// Query blockIdx.x * 32 + threadIdx.x / 8.  best[i] = (distance, train, second, 0), all kNone without a candidate.
 __global__ __launch_bounds__(kGuBlock) void k_guided_search(MaSide Q, MaSide T, GuidedGrid g, const float4* __restrict__ win,
                                                             const uint32_t* __restrict__ qnorm, const uint32_t* __restrict__ start,
                                                             const uint4* __restrict__ ordered, uint4* __restrict__ best) {
     const char *qrecs, *trecs;
-    const unsigned nq = ma_resolve(Q, qrecs);
-    (void)ma_resolve(T, trecs);
+    const unsigned nq = list_resolve(Q, qrecs);
+    (void)list_resolve(T, trecs);
     const unsigned sub = threadIdx.x & (kGuLanes - 1);
     const unsigned i = blockIdx.x * (kGuBlock / kGuLanes) + threadIdx.x / kGuLanes;
     if (i >= nq) return;  // uniform in the group of eight lanes
     const uint4 qd = *reinterpret_cast<const uint4*>(qrecs + (size_t)i * kMaRecord + kMaDesc + 16u * sub);
     const uint32_t qn = qnorm[i];
     const float4 box = win[i];  // x0, x1, y0, y1
-    uint32_t B = kGuNone, I = kGuNone, S = kGuNone;
+    uint32_t B = kNone, I = kNone, S = kNone;
     if (box.x <= box.y && box.z <= box.w) {  // false for a NaN: such a window has no candidate
         const unsigned cx0 = gu_cell(box.x, g.inv_side, g.xmax), cx1 = gu_cell(box.y, g.inv_side, g.xmax);
         const unsigned cy0 = gu_cell(box.z, g.inv_side, g.ymax), cy1 = gu_cell(box.w, g.inv_side, g.ymax);
@@ -208,21 +196,14 @@ __global__ __launch_bounds__(kGuBlock) void k_guided_search(MaSide Q, MaSide T, 
     if (sub == 0) best[i] = make_uint4(B, I, S, 0u);
 }
 
-// steps 5's "no candidate" and 6 of the rule
-__device__ __forceinline__ bool gu_passes(const uint4 b, int use_ratio, float r2, uint32_t max_distance) {
-    bool keep = b.y != kGuNone;
-    if (use_ratio) keep = keep && __uint2float_rn(b.x) < r2 * __uint2float_rn(b.z);  // (float)0xffffffff is 2^32
-    return keep && b.x <= max_distance;
-}
-
 __global__ __launch_bounds__(256) void k_guided_claim(MaSide Q, const uint4* __restrict__ best, int use_ratio, float r2,
                                                       uint32_t max_distance, unsigned long long* __restrict__ tmin) {
     const char* recs;
-    const unsigned nq = ma_resolve(Q, recs);
+    const unsigned nq = list_resolve(Q, recs);
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     if (i >= nq) return;
     const uint4 b = best[i];
-    if (gu_passes(b, use_ratio, r2, max_distance)) atomicMin(tmin + b.y, ((unsigned long long)b.x << 32) | i);  // b.y < nt
+    if (passes_ratio_and_cap(b.x, b.y, b.z, use_ratio, r2, max_distance)) atomicMin(tmin + b.y, ((unsigned long long)b.x << 32) | i);  // b.y < nt
 }
 
 __global__ __launch_bounds__(256) void k_guided_select(MaSide Q, const uint4* __restrict__ best, const float2* __restrict__ qxy,
@@ -230,15 +211,15 @@ __global__ __launch_bounds__(256) void k_guided_select(MaSide Q, const uint4* __
                                                        int unique, const unsigned long long* __restrict__ tmin,
                                                        uint4* __restrict__ out, uint32_t* __restrict__ out_count) {
     const char* recs;
-    const unsigned nq = ma_resolve(Q, recs);
+    const unsigned nq = list_resolve(Q, recs);
     const unsigned first = blockIdx.x * 256u + (threadIdx.x & ~63u);
     if (first >= nq) return;  // wave-uniform
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     bool keep = i < nq;
-    uint4 b = make_uint4(kGuNone, kGuNone, kGuNone, 0u);
+    uint4 b = make_uint4(kNone, kNone, kNone, 0u);
     if (keep) {
         b = best[i];
-        keep = gu_passes(b, use_ratio, r2, max_distance);
+        keep = passes_ratio_and_cap(b.x, b.y, b.z, use_ratio, r2, max_distance);
     }
     if (keep && unique) keep = tmin[b.y] == (((unsigned long long)b.x << 32) | i);
     uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
@@ -247,16 +228,5 @@ __global__ __launch_bounds__(256) void k_guided_select(MaSide Q, const uint4* __
         lo = make_uint4(i, b.y, b.x, b.z);
         hi = make_uint4(__float_as_uint(q.x), __float_as_uint(q.y), __float_as_uint(t.x), __float_as_uint(t.y));
     }
-    // compaction per wave: one ballot, one atomic
-    const unsigned long long mask = __ballot(keep);
-    if (mask == 0) return;
-    const unsigned lane = threadIdx.x & 63u;
-    uint32_t slot = 0;
-    if (lane == 0) slot = atomicAdd(out_count, (uint32_t)__popcll(mask));
-    slot = (uint32_t)__shfl((int)slot, 0);
-    if (keep) {
-        slot += (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-        out[2 * (size_t)slot] = lo;      // at most nq <= the query capacity records: the buffer cannot overflow
-        out[2 * (size_t)slot + 1] = hi;
-    }
+    emit_match_record(keep, lo, hi, out, out_count);  // at most nq <= the query capacity records
 }

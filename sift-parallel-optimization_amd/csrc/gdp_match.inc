@@ -27,40 +27,14 @@ constexpr int kMaBlock = 64 * kMaWaves;
 constexpr int kMaChunkUnit = 128;      // a chunk of the other list is a multiple of this many records
 constexpr int kMaWindow = 512;         // records per packed-key window (9 index bits)
 constexpr int kMaTargetWaves = 4096;   // chunks are added until the capacity grid has this many waves
-constexpr uint32_t kMaNone = 0xffffffffu;    // no candidate: a key, a distance or an index
-constexpr uint32_t kMaNoList = 0xffffffffu;  // d_in_count: this side reads its describe object's list
 constexpr unsigned kMaRecord = 176, kMaDesc = 48;  // sizeof(gdp_keypoint_described), offsetof(desc)
 
 typedef int ma_i32x4 __attribute__((ext_vector_type(4)));
 typedef int ma_i32x16 __attribute__((ext_vector_type(16)));
 
-// One side of a match: the caller's list when its count is not kMaNoList, else the first
-// min(counter, both capacities) records of the describe object's image.
-struct MaSide {
-    const char* src;
-    const uint32_t* src_count;
-    unsigned src_cap;  // min(the describe object's capacity, this side's capacity)
-    const char* own;
-    const uint32_t* own_count;
-};
-
-__device__ __forceinline__ unsigned ma_resolve(const MaSide& s, const char*& recs) {
-    const uint32_t own = *s.own_count;
-    if (own != kMaNoList) {
-        recs = s.own;
-        return own;
-    }
-    recs = s.src;
-    const uint32_t n = *s.src_count;
-    return n < s.src_cap ? n : s.src_cap;
-}
-
-// chunk length for a list of n records cut into at most `chunks` chunks: the same expression in
-// k_match_nn and k_match_select (and in tests/test_gpu_match.py)
-__device__ __forceinline__ unsigned ma_chunk_len(unsigned n, unsigned chunks) {
-    const unsigned per = (n + chunks - 1) / chunks;
-    return (per + kMaChunkUnit - 1) / kMaChunkUnit * kMaChunkUnit;
-}
+// One side of a match: the caller's list, else the describe object's image (gdp_pairs.inc).  A type of
+// its own, so that the kernels' symbols name the stage's list
+struct MaSide : ListRef<const char*> {};
 
 // (B, I, S) <- merge with (b, i, s) whose indices all lie ABOVE those already merged: a tie keeps B
 __device__ __forceinline__ void ma_merge_after(uint32_t& B, uint32_t& I, uint32_t& S, uint32_t b, uint32_t i, uint32_t s) {
@@ -87,12 +61,12 @@ __device__ __forceinline__ ma_i32x4 ma_load_frag(const char* p) {
 __global__ __launch_bounds__(256) void k_match_norm(MaSide s0, MaSide s1, uint32_t* __restrict__ norm0, uint32_t* __restrict__ kb0,
                                                     uint32_t* __restrict__ norm1, uint32_t* __restrict__ kb1) {
     const bool second = blockIdx.y != 0;  // field by field: a selected struct would live in scratch
-    const MaSide s = {second ? s1.src : s0.src, second ? s1.src_count : s0.src_count, second ? s1.src_cap : s0.src_cap,
-                      second ? s1.own : s0.own, second ? s1.own_count : s0.own_count};
+    const MaSide s = {{second ? s1.src : s0.src, second ? s1.src_count : s0.src_count, second ? s1.src_cap : s0.src_cap,
+                       second ? s1.own : s0.own, second ? s1.own_count : s0.own_count}};
     uint32_t* norm = second ? norm1 : norm0;
     uint32_t* kb = second ? kb1 : kb0;
     const char* recs;
-    const unsigned n = ma_resolve(s, recs);
+    const unsigned n = list_resolve(s, recs);
     const unsigned j = blockIdx.x * 256u + threadIdx.x;
     if (j >= n) return;
     const uint4* d = reinterpret_cast<const uint4*>(recs + (size_t)j * kMaRecord + kMaDesc);
@@ -119,9 +93,9 @@ __global__ __launch_bounds__(kMaBlock) void k_match_nn(MaSide Q, MaSide T, const
     const unsigned lane = threadIdx.x & 63u, r = lane & 31u, h = lane >> 5;
     const unsigned q0 = (blockIdx.x * kMaWaves + (threadIdx.x >> 6)) * kMaTile;
     const char *qrecs, *trecs;
-    const unsigned nq = ma_resolve(Q, qrecs), nt = ma_resolve(T, trecs);
+    const unsigned nq = list_resolve(Q, qrecs), nt = list_resolve(T, trecs);
     if (q0 >= nq || nt == 0) return;  // wave-uniform: the grid is sized from the capacities
-    const unsigned len = ma_chunk_len(nt, chunks);
+    const unsigned len = chunk_len(nt, chunks, kMaChunkUnit);
     const unsigned long long begin = (unsigned long long)blockIdx.y * len;
     if (begin >= nt) return;
     const unsigned t_begin = (unsigned)begin, t_end = nt - t_begin < len ? nt : t_begin + len;
@@ -136,8 +110,8 @@ __global__ __launch_bounds__(kMaBlock) void k_match_nn(MaSide Q, MaSide T, const
     ma_i32x16 cinit;
     for (int e = 0; e < 16; ++e) cinit[e] = -(int)(nqv >> 1);
 
-    uint32_t B = kMaNone, I = kMaNone, S = kMaNone;  // the full triple of this lane's rows
-    uint32_t kb1 = kMaNone, kb2 = kMaNone;           // the smallest two keys of the current window
+    uint32_t B = kNone, I = kNone, S = kNone;  // the full triple of this lane's rows
+    uint32_t kb1 = kNone, kb2 = kNone;           // the smallest two keys of the current window
 
     ma_i32x4 tf[4];
     uint4 kbv[4];
@@ -161,7 +135,7 @@ __global__ __launch_bounds__(kMaBlock) void k_match_nn(MaSide Q, MaSide T, const
                 // kb - (acc << 10); |acc| < 2^22, so the 24-bit multiply is exact (the compiler emits a shift and a subtract)
                 uint32_t key = (uint32_t)__mul24(acc[4 * g + e], -1024) + kw[e];
                 if constexpr (decltype(masked)::value)
-                    if (j0 + 8u * g + 4u * h + e >= t_end) key = kMaNone;
+                    if (j0 + 8u * g + 4u * h + e >= t_end) key = kNone;
                 const uint32_t hi = key > kb1 ? key : kb1;
                 kb2 = kb2 < hi ? kb2 : hi;
                 kb1 = kb1 < key ? kb1 : key;
@@ -170,10 +144,10 @@ __global__ __launch_bounds__(kMaBlock) void k_match_nn(MaSide Q, MaSide T, const
     };
     auto fold_window = [&](unsigned j0) {  // the window's two keys into the full triple
         const uint32_t base = j0 & ~(uint32_t)(kMaWindow - 1);
-        const uint32_t d1 = kb1 == kMaNone ? kMaNone : (kb1 >> 9) - 1u + par;
-        const uint32_t d2 = kb2 == kMaNone ? kMaNone : (kb2 >> 9) - 1u + par;
+        const uint32_t d1 = kb1 == kNone ? kNone : (kb1 >> 9) - 1u + par;
+        const uint32_t d2 = kb2 == kNone ? kNone : (kb2 >> 9) - 1u + par;
         ma_merge_after(B, I, S, d1, base + (kb1 & (kMaWindow - 1)), d2);
-        kb1 = kb2 = kMaNone;
+        kb1 = kb2 = kNone;
     };
     load_tile(t_begin, tf, kbv);
     unsigned j0 = t_begin;
@@ -211,25 +185,23 @@ __global__ __launch_bounds__(256) void k_match_select(MaSide Q, MaSide T, const 
                                                       unsigned qchunks, int use_ratio, float r2, uint32_t max_distance, int mutual,
                                                       uint4* __restrict__ out, uint32_t* __restrict__ out_count) {
     const char *qrecs, *trecs;
-    const unsigned nq = ma_resolve(Q, qrecs), nt = ma_resolve(T, trecs);
+    const unsigned nq = list_resolve(Q, qrecs), nt = list_resolve(T, trecs);
     const unsigned first = blockIdx.x * 256u + (threadIdx.x & ~63u);
     if (first >= nq || nt == 0) return;  // wave-uniform
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     bool keep = i < nq;
-    uint32_t B = kMaNone, I = kMaNone, S = kMaNone;
+    uint32_t B = kNone, I = kNone, S = kNone;
     if (keep) {
-        const unsigned len = ma_chunk_len(nt, tchunks), used = (nt + len - 1) / len;
+        const unsigned len = chunk_len(nt, tchunks, kMaChunkUnit), used = (nt + len - 1) / len;
         for (unsigned c = 0; c < used; ++c) {  // ascending chunks hold ascending indices
             const uint4 p = part[(size_t)c * qpad + i];
             ma_merge_after(B, I, S, p.x, p.y, p.z);
         }
-        // the ratio test: one rounded product and one comparison; (float)0xffffffff is 2^32
-        if (use_ratio) keep = __uint2float_rn(B) < r2 * __uint2float_rn(S);
-        keep = keep && B <= max_distance && I < nt;  // I < nt always holds: nt >= 1 gave every query a candidate
+        keep = passes_ratio_and_cap(B, I, S, use_ratio, r2, max_distance) && I < nt;  // I < nt always holds: nt >= 1 gave every query a candidate
     }
     if (keep && mutual) {  // is i the nearest query of train I, ties to the lowest query?
-        const unsigned len = ma_chunk_len(nq, qchunks), used = (nq + len - 1) / len;
-        uint32_t mB = kMaNone, mI = kMaNone, mS = kMaNone;
+        const unsigned len = chunk_len(nq, qchunks, kMaChunkUnit), used = (nq + len - 1) / len;
+        uint32_t mB = kNone, mI = kNone, mS = kNone;
         for (unsigned c = 0; c < used; ++c) {
             const uint4 p = mpart[(size_t)c * tpad + I];
             ma_merge_after(mB, mI, mS, p.x, p.y, p.z);
@@ -238,27 +210,11 @@ __global__ __launch_bounds__(256) void k_match_select(MaSide Q, MaSide T, const 
     }
     uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
     if (keep) {
-        float xy[4];
-        for (int side = 0; side < 2; ++side) {
-            const uint4* rec = reinterpret_cast<const uint4*>((side ? trecs : qrecs) + (size_t)(side ? I : i) * kMaRecord);
-            const uint4 w0 = rec[0], w1 = rec[1];  // octave | scale | kind, row, col, value;  dscale, drow, dcol, interp
-            const float sc = (float)(1u << (w0.x & 31u));
-            xy[2 * side] = ((float)(int)w0.z + __uint_as_float(w1.z)) * sc;
-            xy[2 * side + 1] = ((float)(int)w0.y + __uint_as_float(w1.y)) * sc;
-        }
+        float qx, qy, tx, ty;
+        record_xy(qrecs + (size_t)i * kMaRecord, qx, qy);
+        record_xy(trecs + (size_t)I * kMaRecord, tx, ty);
         lo = make_uint4(i, I, B, S);
-        hi = make_uint4(__float_as_uint(xy[0]), __float_as_uint(xy[1]), __float_as_uint(xy[2]), __float_as_uint(xy[3]));
+        hi = make_uint4(__float_as_uint(qx), __float_as_uint(qy), __float_as_uint(tx), __float_as_uint(ty));
     }
-    // compaction per wave: one ballot, one atomic
-    const unsigned long long mask = __ballot(keep);
-    if (mask == 0) return;
-    const unsigned lane = threadIdx.x & 63u;
-    uint32_t slot = 0;
-    if (lane == 0) slot = atomicAdd(out_count, (uint32_t)__popcll(mask));
-    slot = (uint32_t)__shfl((int)slot, 0);
-    if (keep) {
-        slot += (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-        out[2 * (size_t)slot] = lo;      // at most nq <= the query capacity records: the buffer cannot overflow
-        out[2 * (size_t)slot + 1] = hi;
-    }
+    emit_match_record(keep, lo, hi, out, out_count);  // at most nq <= the query capacity records
 }

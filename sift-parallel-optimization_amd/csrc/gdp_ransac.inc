@@ -17,37 +17,10 @@ constexpr int kRaHypTile = 256;        // hypotheses (threads) per block of k_ra
 constexpr int kRaMatchTile = 64;       // a chunk of the match list is a multiple of this many records
 constexpr int kRaGroup = 8;            // matches whose scalar loads are issued together
 constexpr int kRaTargetWaves = 8192;   // chunks are added until the capacity grid has this many waves
-constexpr uint32_t kRaNone = 0xffffffffu;    // no model: a hypothesis index, a sample index
-constexpr uint32_t kRaNoList = 0xffffffffu;  // d_in_count: the fit reads the match object's list
 constexpr uint32_t kRaMaxHypotheses = 65536, kRaDefaultHypotheses = 4096;
 
-// The list a fit reads: the caller's when its count is not kRaNoList, else the first
-// min(counter, both capacities) records of the match object's output.
-struct RaList {
-    const uint4* src;
-    const uint32_t* src_count;
-    unsigned src_cap;  // min(the match object's query capacity, this object's capacity)
-    const uint4* own;
-    const uint32_t* own_count;
-};
-
-__device__ __forceinline__ unsigned ra_resolve(const RaList& s, const uint4*& recs) {
-    const uint32_t own = *s.own_count;
-    if (own != kRaNoList) {
-        recs = s.own;
-        return own;
-    }
-    recs = s.src;
-    const uint32_t n = *s.src_count;
-    return n < s.src_cap ? n : s.src_cap;
-}
-
-// chunk length for a list of n records cut into at most `chunks` chunks: the same expression in
-// k_ransac_score and in tests/test_gpu_ransac.py
-__device__ __forceinline__ unsigned ra_chunk_len(unsigned n, unsigned chunks) {
-    const unsigned per = (n + chunks - 1) / chunks;
-    return (per + kRaMatchTile - 1) / kRaMatchTile * kRaMatchTile;
-}
+// The list a fit reads: the caller's, else the match object's output (gdp_pairs.inc); its own type as MaSide is
+struct RaList : ListRef<const uint4*> {};
 
 __device__ __forceinline__ uint32_t ra_mix(uint32_t x) {
     x ^= x >> 16;
@@ -87,9 +60,8 @@ __device__ __forceinline__ void ra_basis(const double (&x)[4], const double (&y)
 
 // step 5 for one pair: the same expression in k_ransac_score and k_ransac_inliers
 __device__ __forceinline__ bool ra_inlier(const float (&h)[9], float x, float y, float X, float Y, float tt) {
-    const float u = (h[0] * x + h[1] * y) + h[2];
-    const float v = (h[3] * x + h[4] * y) + h[5];
-    const float w = (h[6] * x + h[7] * y) + h[8];
+    float u, v, w;
+    project(h, x, y, u, v, w);
     const float dx = X * w - u;
     const float dy = Y * w - v;
     const float e = dx * dx + dy * dy;
@@ -102,7 +74,7 @@ __global__ __launch_bounds__(kRaHypTile) void k_ransac_fit(RaList L, uint32_t H,
     const uint32_t h = blockIdx.x * (uint32_t)kRaHypTile + threadIdx.x;
     if (h >= H) return;
     const uint4* recs;
-    const unsigned n = ra_resolve(L, recs);
+    const unsigned n = list_resolve(L, recs);
     uint32_t idx[4];
     for (uint32_t k = 0; k < 4; ++k) idx[k] = __umulhi(ra_mix(seed + 0x9e3779b9u * (4u * h + k + 1u)), n);
     bool valid = n >= 4 && idx[0] != idx[1] && idx[0] != idx[2] && idx[0] != idx[3] && idx[1] != idx[2] && idx[1] != idx[3] &&
@@ -158,8 +130,8 @@ __global__ __launch_bounds__(kRaHypTile) void k_ransac_score(RaList L, uint32_t 
     const uint32_t first = blockIdx.x * (uint32_t)kRaHypTile + (threadIdx.x & ~63u);
     if (first >= H) return;  // wave-uniform
     const uint4* recs;
-    const unsigned n = ra_resolve(L, recs);
-    const unsigned len = ra_chunk_len(n, chunks);
+    const unsigned n = list_resolve(L, recs);
+    const unsigned len = chunk_len(n, chunks, kRaMatchTile);
     const unsigned long long begin64 = (unsigned long long)blockIdx.y * len;
     if (begin64 >= n) return;  // covers n == 0
     const unsigned begin = (unsigned)begin64, end = n - begin < len ? n : begin + len;
@@ -218,23 +190,23 @@ __global__ __launch_bounds__(1024) void k_ransac_select(RaList L, uint32_t H, ui
         return;
     }
     const uint4* recs;
-    const unsigned n = ra_resolve(L, recs);
+    const unsigned n = list_resolve(L, recs);
     model[0] = model[1] = make_uint4(0u, 0u, 0u, 0u);
-    model[2] = make_uint4(0u, kRaNone, 0u, n);
-    model[3] = make_uint4(kRaNone, kRaNone, kRaNone, kRaNone);
+    model[2] = make_uint4(0u, kNone, 0u, n);
+    model[3] = make_uint4(kNone, kNone, kNone, kNone);
 }
 
 // One thread per match; the grid is sized from the capacity.  Writes nothing without a model.
 __global__ __launch_bounds__(256) void k_ransac_inliers(RaList L, float tt, const uint4* __restrict__ model, uint4* __restrict__ out,
                                                         uint32_t* __restrict__ out_count) {
     const uint4* recs;
-    const unsigned n = ra_resolve(L, recs);
+    const unsigned n = list_resolve(L, recs);
     const unsigned first = blockIdx.x * 256u + (threadIdx.x & ~63u);
     if (first >= n) return;  // wave-uniform
-    const uint4 a = model[0], b = model[1], c = model[2];
-    if (c.y == kRaNone) return;
-    const float m[9] = {__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(a.w), __uint_as_float(b.x),
-                        __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w), __uint_as_float(c.x)};
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(model);
+    if (words[9] == kNone) return;  // the record's `hypothesis`
+    float m[9];
+    load_model(words, nullptr, m);
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     bool keep = i < n;
     uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
@@ -243,16 +215,5 @@ __global__ __launch_bounds__(256) void k_ransac_inliers(RaList L, float tt, cons
         hi = recs[2 * (size_t)i + 1];
         keep = ra_inlier(m, __uint_as_float(hi.x), __uint_as_float(hi.y), __uint_as_float(hi.z), __uint_as_float(hi.w), tt);
     }
-    // compaction per wave: one ballot, one atomic
-    const unsigned long long mask = __ballot(keep);
-    if (mask == 0) return;
-    const unsigned lane = threadIdx.x & 63u;
-    uint32_t slot = 0;
-    if (lane == 0) slot = atomicAdd(out_count, (uint32_t)__popcll(mask));
-    slot = (uint32_t)__shfl((int)slot, 0);
-    if (keep) {
-        slot += (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-        out[2 * (size_t)slot] = lo;  // at most n <= the capacity records: the buffer cannot overflow
-        out[2 * (size_t)slot + 1] = hi;
-    }
+    emit_match_record(keep, lo, hi, out, out_count);  // at most n <= the capacity records
 }

@@ -20,8 +20,6 @@ constexpr int kWpTileCols = 32;    // its columns
 constexpr int kWpLanePixels = 4;   // consecutive columns per lane
 constexpr int kWpBlockRows = 16, kWpBlockCols = 64;  // 2 x 2 wave tiles
 constexpr int kWpMaxDim = 1 << 24; // (float)(W - 1) is exact up to here: step 6 rests on it
-constexpr uint32_t kWpNone = 0xffffffffu;  // the fit's model record without a model
-static_assert(kWpNone == kRaNone, "the sentinel k_ransac_select stores");
 
 struct WarpGeom {
     const void* src;       // the source image's first pixel
@@ -41,11 +39,9 @@ __global__ void k_warp_prepare(const uint32_t* __restrict__ model, const float* 
                                gdp_warp_record* __restrict__ rec) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     float h[9], m[9];
-    bool valid = own != nullptr || model[9] != kWpNone;
-    for (int k = 0; k < 9; ++k) {
-        h[k] = own ? own[k] : __uint_as_float(model[k]);
-        m[k] = h[k];
-    }
+    bool valid = own != nullptr || model[9] != kNone;  // kNone: the hypothesis k_ransac_select stores without a model
+    load_model(model, own, h);
+    for (int k = 0; k < 9; ++k) m[k] = h[k];
     if (valid && direction == 1) {
         double M[3][3], G[3][3];
         for (int r = 0; r < 3; ++r)
@@ -124,9 +120,8 @@ __global__ __launch_bounds__(256) void k_warp(WarpGeom g, const uint32_t* __rest
             const float y = (float)r;
             for (int k = 0; k < kWpLanePixels; ++k) {
                 const float x = (float)(c0 + (unsigned)k);
-                const float u = (m[0] * x + m[1] * y) + m[2];
-                const float v = (m[3] * x + m[4] * y) + m[5];
-                const float w = (m[6] * x + m[7] * y) + m[8];
+                float u, v, w;
+                project(m, x, y, u, v, w);
                 sx[k] = u / w;
                 sy[k] = v / w;
                 // a NaN fails every comparison

@@ -611,6 +611,15 @@ class PyramidContext:
     def _warp_handle(self):
         return self._handle("warp")
 
+    def _set_model(self, name, h):
+        """set_warp_model and set_guided_model: nine floats, or None, to the `name` object's gdp_<name>_set_model."""
+        obj = self._handle(name)
+        if h is not None:
+            h = np.ascontiguousarray(h, dtype=np.float32).reshape(-1)
+            if h.size != 9:
+                raise ValueError(f"a {name} model is nine floats")
+        check(getattr(lib(), f"gdp_{name}_set_model")(obj, None if h is None else _ptr(h)), obj, name)
+
     def _set_capacity(self, name, capacity):
         self._drop(name)  # the next use creates it again, of the new size
         self._capacity[name] = capacity
@@ -903,14 +912,7 @@ class PyramidContext:
         """Make the nine floats of `h` (3 x 3 or flat, row-major, query -> train) the model a guided
         match reads instead of the fit's model record (blocking; the floats are not validated); None
         goes back to the fit's record."""
-        g = self._handle("guided")
-        if h is None:
-            check(lib().gdp_guided_set_model(g, None), g, "guided")
-            return
-        h = np.ascontiguousarray(h, dtype=np.float32).reshape(-1)
-        if h.size != 9:
-            raise ValueError("a guided model is nine floats")
-        check(lib().gdp_guided_set_model(g, _ptr(h)), g, "guided")
+        self._set_model("guided", h)
 
     def guided_count(self):
         """Records the last guided match produced (blocking; 0 before any)."""
@@ -954,14 +956,7 @@ class PyramidContext:
         """Make the nine floats of `h` (3 x 3 or flat, row-major, query -> train) the model a warp
         reads instead of the fit's model record (blocking; the floats are not validated); None goes
         back to the fit's."""
-        w = self._handle("warp")
-        if h is None:
-            check(lib().gdp_warp_set_model(w, None), w, "warp")
-            return
-        h = np.ascontiguousarray(h, dtype=np.float32).reshape(-1)
-        if h.size != 9:
-            raise ValueError("a warp model is nine floats")
-        check(lib().gdp_warp_set_model(w, _ptr(h)), w, "warp")
+        self._set_model("warp", h)
 
     def warp_record(self):
         """The last warp's WARP_DTYPE record (blocking; all 0 before any)."""

@@ -15,11 +15,14 @@ Call = namedtuple("Call", "name handles ints")
 GEOMETRY = (16, 16, 2, 2, 1)  # H, W, S, O, B of every stand-in context
 LEVEL_DIMS = (8, 8, 0)
 LAST_ERROR = {"ctx": "gdp_last_error", "orient": "gdp_orient_last_error", "describe": "gdp_describe_last_error",
-              "match": "gdp_match_last_error", "ransac": "gdp_ransac_last_error", "warp": "gdp_warp_last_error"}
+              "match": "gdp_match_last_error", "ransac": "gdp_ransac_last_error", "warp": "gdp_warp_last_error",
+              "guided": "gdp_guided_last_error"}
 CREATES = ("gdp_create_band", "gdp_orient_create", "gdp_describe_create", "gdp_match_create", "gdp_ransac_create",
            "gdp_warp_create")
 DESTROYS = ("gdp_destroy", "gdp_orient_destroy", "gdp_describe_destroy", "gdp_match_destroy", "gdp_ransac_destroy",
             "gdp_warp_destroy")
+# the guided object, which _use_every_stage does not make: the cases that walk CREATES count one object of each kind
+GUIDED_CREATE, GUIDED_DESTROY = "gdp_guided_create", "gdp_guided_destroy"
 
 
 class StandIn:
@@ -52,14 +55,14 @@ class StandIn:
         if name == "gdp_status_string":
             return b"status string %d" % args[0]
         status = self.status.get(name, 0)
-        if name in CREATES and not status:
+        if (name in CREATES or name == GUIDED_CREATE) and not status:
             self._next += 0x10
             outs[0].value = self._next
             self.live.add(self._next)
             self.created.setdefault(name, []).append(self._next)
             handles = (self._next,) + tuple(h for h in handles if h is not None)
         self.calls.append(Call(name, handles, ints))
-        if name in DESTROYS:
+        if name in DESTROYS or name == GUIDED_DESTROY:
             return None
         if status:
             return status
@@ -83,7 +86,7 @@ class StandIn:
         return list(self.created.get(export, ()))
 
     def destroyed(self, since=0):
-        return [(c.name, c.handles[0]) for c in self.calls[since:] if c.name in DESTROYS]
+        return [(c.name, c.handles[0]) for c in self.calls[since:] if c.name in DESTROYS or c.name == GUIDED_DESTROY]
 
     def last(self, export):
         return [c for c in self.calls if c.name == export][-1]
@@ -212,6 +215,34 @@ def test_set_ransac_capacity_drops_ransac_and_warp_only(gdp):
     assert len(fake.made("gdp_match_create")) == 1
     with pytest.raises(ValueError, match="a RANSAC capacity must be >= 0"):
         ctx.set_ransac_capacity(0, -1)
+
+
+def test_the_guided_object_reads_the_fit_object_and_goes_before_it(gdp):
+    fake, context = gdp
+    ctx = context()
+    _use_every_stage(ctx)
+    ctx.guided_match(3.0)
+    h = dict(_chain(fake), guided=fake.made(GUIDED_CREATE)[0])
+    assert fake.last("gdp_guided_create").handles == (h["guided"], h["ransac"]) and fake.last("gdp_guided_create").ints == (0,)
+    assert fake.last("gdp_match_guided").handles == (h["guided"], None)
+    ctx.set_guided_capacity(64)  # drops the guided object alone
+    assert fake.destroyed() == [("gdp_guided_destroy", h["guided"])]
+    ctx.guided_match(3.0)
+    new = fake.last("gdp_guided_create")
+    assert new.handles == (new.handles[0], h["ransac"]) and new.ints == (64,) and new.handles[0] != h["guided"]
+    n = len(fake.calls)
+    ctx.set_ransac_capacity(7, 9)  # the fit object's two readers go first, in the order they are listed
+    assert fake.destroyed(n) == [("gdp_warp_destroy", h["warp"]), ("gdp_guided_destroy", new.handles[0]), ("gdp_ransac_destroy", h["ransac"])]
+    ctx.guided_match(3.0)  # the fit object is made again on the way to the guided object; no warp object is
+    fit, last = fake.last("gdp_ransac_create").handles[0], fake.last("gdp_guided_create").handles[0]
+    assert fake.last("gdp_guided_create").handles == (last, fit) and len(fake.made("gdp_warp_create")) == 1
+    n = len(fake.calls)
+    ctx.close()
+    assert fake.destroyed(n) == [("gdp_guided_destroy", last), ("gdp_ransac_destroy", fit), ("gdp_match_destroy", h["match"]),
+                                 ("gdp_describe_destroy", h["describe"]), ("gdp_orient_destroy", h["orient"]),
+                                 ("gdp_destroy", fake.made("gdp_create_band")[0])]
+    with pytest.raises(ValueError, match="a cell count must be >= 0"):
+        ctx.set_guided_capacity(-1)
 
 
 def test_a_train_context_drops_the_match_objects_of_other_contexts_first(gdp):
@@ -356,7 +387,8 @@ ROUTES = {"ctx": ("gdp_create_band", "build", "gdp_build"),
           "describe": ("gdp_describe_create", "describe_keypoints", "gdp_describe_keypoints"),
           "match": ("gdp_match_create", "match_descriptors", "gdp_match_descriptors"),
           "ransac": ("gdp_ransac_create", "fit_homography", "gdp_fit_homography"),
-          "warp": ("gdp_warp_create", "warp_image", "gdp_warp_image")}
+          "warp": ("gdp_warp_create", "warp_image", "gdp_warp_image"),
+          "guided": ("gdp_guided_create", "guided_layout", "gdp_guided_layout")}  # guided_match takes an argument
 
 
 @pytest.mark.parametrize("kind", sorted(ROUTES))
