@@ -128,6 +128,16 @@ public:
     // object lives for the call only.
     gdp_homography FitHomography(const std::vector<gdp_match_record>& matches, std::vector<gdp_match_record>* inliers = nullptr,
                                  uint32_t hypotheses = 1024, uint32_t seed = 0, float threshold = 3.0f, uint32_t min_inliers = 4);
+    // Extension: FitHomography followed, on the same fit object and stream with no host read in between,
+    // by `rounds` (1..8) rounds of the least-squares refit of the model over its inliers
+    // (gdp_refit_homography in gdp.h has the exact rule: exact 128-bit integer moments of the inlier
+    // coordinates quantised to 1/256 px, one 8 x 8 solve in float64; a round's candidate replaces the
+    // model and the inliers when it accepts at least as many matches under `refit_threshold`).  Returns
+    // the model record after the refit; *inliers as for FitHomography, *record (when not NULL) the
+    // refit record.  hypothesis and sample[] stay the RANSAC winner's.
+    gdp_homography RefitHomography(const std::vector<gdp_match_record>& matches, std::vector<gdp_match_record>* inliers = nullptr,
+                                   gdp_refit_record* record = nullptr, uint32_t rounds = 1, float refit_threshold = 3.0f,
+                                   uint32_t hypotheses = 1024, uint32_t seed = 0, float threshold = 3.0f, uint32_t min_inliers = 4);
     // Extension: `other`'s input image resampled into this pyramid's frame (GDP_WARP_TRAIN_TO_QUERY), or
     // this pyramid's into `other`'s (GDP_WARP_QUERY_TO_TRAIN, under the normalised adjugate), on the
     // device (gdp_warp_image in gdp.h has the exact rule: `h` maps this pyramid's (x, y) to `other`'s,
@@ -303,6 +313,10 @@ protected:
         out.resize(stored);
         return out;
     }
+    // FitHomography and RefitHomography: one fit object for the call, `rounds` = 0 without the refit
+    gdp_homography fit_(const char* what, const std::vector<gdp_match_record>& matches, std::vector<gdp_match_record>* inliers,
+                        uint32_t hypotheses, uint32_t seed, float threshold, uint32_t min_inliers, uint32_t rounds, float refit_threshold,
+                        gdp_refit_record* record);
     static int download_refined_(gdp_ctx* c, int b, gdp_keypoint_refined* host, size_t capacity, size_t* stored, size_t*) {
         return gdp_download_refined(c, b, host, capacity, stored);  // the one list without a `found` output
     }
@@ -509,7 +523,19 @@ inline std::vector<gdp_match_record> GaussPyramid_hip::MatchDescriptors(GaussPyr
 
 inline gdp_homography GaussPyramid_hip::FitHomography(const std::vector<gdp_match_record>& matches, std::vector<gdp_match_record>* inliers,
                                                       uint32_t hypotheses, uint32_t seed, float threshold, uint32_t min_inliers) {
-    const char* const what = "FitHomography";
+    return fit_("FitHomography", matches, inliers, hypotheses, seed, threshold, min_inliers, 0, 0.0f, nullptr);
+}
+
+inline gdp_homography GaussPyramid_hip::RefitHomography(const std::vector<gdp_match_record>& matches, std::vector<gdp_match_record>* inliers,
+                                                        gdp_refit_record* record, uint32_t rounds, float refit_threshold,
+                                                        uint32_t hypotheses, uint32_t seed, float threshold, uint32_t min_inliers) {
+    if (rounds == 0) fail_("RefitHomography", "rounds must be in 1..8", GDP_ERR_ARG);
+    return fit_("RefitHomography", matches, inliers, hypotheses, seed, threshold, min_inliers, rounds, refit_threshold, record);
+}
+
+inline gdp_homography GaussPyramid_hip::fit_(const char* what, const std::vector<gdp_match_record>& matches,
+                                             std::vector<gdp_match_record>* inliers, uint32_t hypotheses, uint32_t seed, float threshold,
+                                             uint32_t min_inliers, uint32_t rounds, float refit_threshold, gdp_refit_record* record) {
     ensure_described_(what);
     const size_t n = matches.size(), cap = n ? n : 1;
     gdp_match* m = nullptr;  // the fit object is made from a match object; its own list is never read here
@@ -519,8 +545,10 @@ inline gdp_homography GaussPyramid_hip::FitHomography(const std::vector<gdp_matc
     const gdp_match_record none{};
     check_(what, gdp_ransac_last_error, r, gdp_ransac_set_input(r, n ? matches.data() : &none, n));
     check_(what, gdp_ransac_last_error, r, gdp_fit_homography(r, hypotheses, seed, threshold, min_inliers, nullptr));
+    if (rounds) check_(what, gdp_ransac_last_error, r, gdp_refit_homography(r, rounds, refit_threshold, nullptr));
     gdp_homography model;
     check_(what, gdp_ransac_last_error, r, gdp_download_homography(r, &model));
+    if (record) check_(what, gdp_ransac_last_error, r, gdp_download_refit(r, record));
     if (inliers) *inliers = list_<gdp_match_record>(what, gdp_ransac_last_error, r, gdp_ransac_count, gdp_download_inliers);
     gdp_ransac_destroy(r);
     gdp_match_destroy(m);

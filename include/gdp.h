@@ -679,8 +679,9 @@ int gdp_match_layout(const gdp_match* m, size_t* query_capacity, size_t* train_c
  * parameters, and the counts are integer sums, so the result is an exact set, independent of tiling
  * and wave timing.  For a list the pipeline produced (the match object's) that order is the device
  * order (gdp_device_matches), which is unspecified, as with `query` / `train` of the matches; for a
- * list the caller supplied (gdp_ransac_set_input) it is exactly the caller's.  Out of scope:
- * least-squares refinement over the inliers, early termination, other models. */
+ * list the caller supplied (gdp_ransac_set_input) it is exactly the caller's.  The model is the
+ * exact homography of four matches; gdp_refit_homography (below) refits it over the inliers by least
+ * squares.  Out of scope: early termination, other models. */
 typedef struct gdp_homography {   /* 64 bytes, four 16-B stores */
     float    h[9];                /* row-major, as scored: max |h| in [0.5, 1]; all 0 = invalid / none */
     uint32_t hypothesis;          /* its index; 0xffffffff in the model record when there is none */
@@ -735,6 +736,95 @@ int gdp_device_inliers(const gdp_ransac* r, const gdp_match_record** records, co
  * hypotheses per block of the scoring sweep, one per lane. */
 int gdp_ransac_layout(const gdp_ransac* r, size_t* capacity, uint32_t* max_hypotheses,
                       uint32_t* match_tile, uint32_t* hypothesis_tile);
+
+/* ---- extension: least-squares refit of the fitted homography on the device ----------------------
+ * What every user of a RANSAC homography does next: the model above is the exact map of four sampled
+ * matches, and the algebraic least-squares homography of ALL its inliers is far closer to the true
+ * one.  It is a second entry point on the fit object: it replaces the model record and the inlier
+ * list IN PLACE, stream-ordered behind gdp_fit_homography, so gdp_warp_image, gdp_match_guided,
+ * gdp_download_homography, gdp_download_inliers and gdp_device_inliers consume the refit model
+ * unchanged and the host reads nothing.  A float reduction over thousands of records has no fixed
+ * order; this one is done in exact integers, so the result is an exact set like the fit's.
+ *
+ * The rule.  M[0..n) is the list as the fit resolves it at launch (the caller's, else the first
+ * min(counter, capacities) records of the match object), L the object's inlier list as it stands, m
+ * the model record, t the `threshold`.  When m says "none" (hypothesis == 0xffffffff) every round
+ * does nothing and status = 6.  Otherwise each of the `rounds` rounds runs:
+ *   1 quantise      (integers.)  A record of L is USED when each of qx, qy, tx, ty is finite with
+ *                   |f| < 16384, else SKIPPED.  q[k] = (int64)rint(f[k] * 256.0f), k = x, y, X, Y: the
+ *                   float32 product is exact and rint is to nearest even
+ *   2 origin        o[k] = floor(sum q[k] / used) over the used records, rounding toward -infinity.
+ *                   Fewer than 4 used records: NO CANDIDATE (status 2; kq, kt, origin, h are 0)
+ *   3 moments       (exact signed 128-bit integers.)  c = q - o.  With mono = (1, cx, cy, cx*cx, cx*cy,
+ *                   cy*cy) indexed a = 0..5 and tmono = (1, cX, cY, cX*cX + cY*cY) indexed b = 0..3,
+ *                   mu[a][b] = sum over the used records of mono[a] * tmono[b]: 24 sums.  |c| < 2^23, so
+ *                   a term is < 2^93 and a sum of at most 2^30 terms < 2^123
+ *   4 scale         kq = the smallest k >= 0 with mu[3][0] + mu[5][0] < used * 4^k, kt the same from
+ *                   mu[0][3]: integer comparisons.  deg_q = (0, 1, 1, 2, 2, 2)[a], deg_t = (0, 1, 1, 2)[b]
+ *   5 solve         (float64, every + - * / separately rounded, no contraction, no sqrt.)
+ *                   S[a][b] = ldexp(+-((double)hi64 * 2^64 + (double)lo64), -(kq * deg_q + kt * deg_t)),
+ *                   hi64 and lo64 the halves of |mu[a][b]| converted to nearest even, the sign mu's.
+ *                   The unknown is g[0..8) with g8 = 1 in the normalised frame, the rows of the
+ *                   inhomogeneous DLT being  x g0 + y g1 + g2 - X x g6 - X y g7 = X  and
+ *                   x g3 + y g4 + g5 - Y x g6 - Y y g7 = Y.  The lower triangle of the 8 x 8 normal matrix
+ *                   N (every entry not listed is +0) and the right-hand side:
+ *                     P = [S[3][0] S[4][0] S[1][0]; S[4][0] S[5][0] S[2][0]; S[1][0] S[2][0] S[0][0]];
+ *                     N[i][j] = N[3+i][3+j] = P[i][j] for j <= i < 3;  for (b, c) = (1, 0) and (2, 3):
+ *                     N[6][c] = -S[3][b], N[6][c+1] = -S[4][b], N[6][c+2] = -S[1][b],
+ *                     N[7][c] = -S[4][b], N[7][c+1] = -S[5][b], N[7][c+2] = -S[2][b],
+ *                     rhs[c] = S[1][b], rhs[c+1] = S[2][b], rhs[c+2] = S[0][b];
+ *                     N[6][6] = S[3][3], N[7][6] = S[4][3], N[7][7] = S[5][3], rhs[6] = -S[1][3], rhs[7] = -S[2][3]
+ *                   LDL^T without pivoting, nothing skipped for being zero: for j = 0..7:
+ *                     v[k] = L[j][k] * D[k] for k < j;  d = N[j][j], then d = d - L[j][k] * v[k] for
+ *                     k = 0..j-1 ascending;  D[j] = d;  a pivot that is not > 0 (a NaN included) gives NO
+ *                     CANDIDATE (status 3);  for i = j+1..7: e = N[i][j], then e = e - L[i][k] * v[k] for
+ *                     k ascending;  L[i][j] = e / d
+ *                   forward, i = 0..7: z[i] = rhs[i], then z[i] = z[i] - L[i][k] * z[k] for k = 0..i-1
+ *                   ascending;  back, i = 7..0: g[i] = z[i] / D[i], then g[i] = g[i] - L[k][i] * g[k] for
+ *                   k = i+1..7 ascending
+ *   6 denormalise   (float64.)  a = 2^(8-kq), bx = ldexp(-(double)o[x], -kq), by likewise from o[y],
+ *                   sc = 2^(kt-8), tX = (double)o[X] / 256, tY = (double)o[Y] / 256: all exact.  With
+ *                   Hh = [g0 g1 g2; g3 g4 g5; g6 g7 1]:
+ *                     K[r][0] = Hh[r][0] * a,  K[r][1] = Hh[r][1] * a,
+ *                     K[r][2] = (Hh[r][0] * bx + Hh[r][1] * by) + Hh[r][2];
+ *                     G[0][c] = sc * K[0][c] + tX * K[2][c],  G[1][c] = sc * K[1][c] + tY * K[2][c],
+ *                     G[2][c] = K[2][c]
+ *                   then step 4 of the fit rule without its sign step (w at the list's origin is g8 = 1):
+ *                   s = max |G|; s 0, infinite or NaN, or a NaN entry: NO CANDIDATE (status 4);
+ *                   else G <- ldexp(G, -e) with s = mant * 2^e (frexp) and h[3r + c] = (float)G[r][c]
+ *   7 accept        c_cur and c_new are the fit rule's step-5 counts of m.h and of the candidate over M
+ *                   under t (c_new = 0 without a candidate).  The candidate is ACCEPTED iff it exists,
+ *                   c_new >= c_cur and c_new >= 4 (status 1; else, with a candidate, status 5).  On
+ *                   acceptance m.h <- the candidate, m.inliers <- c_new, m.matches <- n, and L <- the records
+ *                   of M that step 5 accepts under it; `hypothesis` and `sample[]` keep the RANSAC winner's
+ *                   values.  Otherwise nothing changes, and the later rounds do nothing
+ * As in the fit, nothing but the four floats is read from a record and no address is formed from record
+ * contents.  The sweeps over L and M use min(1024, ceil(capacity / 2048)) blocks of 256 threads. */
+typedef struct gdp_refit_record {   /* 96 bytes, six 16-B stores; all 0 before any refit */
+    uint32_t rounds;              /* rounds requested */
+    uint32_t accepted;            /* rounds accepted */
+    uint32_t used, skipped;       /* step 1's counts in the last round that ran */
+    uint32_t count_before;        /* the first round's c_cur */
+    uint32_t count_after;         /* the model record's `inliers` at the end */
+    uint32_t status;              /* of the last round that ran: 1 accepted, 2 too few used records, 3 pivot,
+                                     4 non-finite, 5 fewer inliers than the model, 6 no model */
+    uint32_t kq, kt;              /* step 4's exponents of the last candidate */
+    int32_t  origin[4];           /* step 2's o[x, y, X, Y] of the last candidate, in 1/256 px */
+    float    h[9];                /* the last candidate as scored, accepted or not (all 0: none) */
+    uint32_t reserved[2];         /* 0 */
+} gdp_refit_record;
+/* Refit: asynchronous and stream-ordered on `stream` (NULL = the query context's own stream), behind
+ * the gdp_fit_homography whose result it replaces; the host reads nothing.  `rounds` must be in 1..8
+ * and `threshold` finite and >= 0, else (a NaN included) GDP_ERR_ARG and nothing changes.  The
+ * refit's buffers are allocated by the object's first refit: that one call allocates device memory,
+ * which synchronises the device, so it cannot be made under stream capture; make one refit before
+ * capturing.  A later gdp_fit_homography gives what it gives without a refit; the refit record stays
+ * that of the last refit. */
+int gdp_refit_homography(gdp_ransac* r, uint32_t rounds, float threshold, void* stream);
+/* The record of the last refit (blocking; all 0 before any). */
+int gdp_download_refit(gdp_ransac* r, gdp_refit_record* rec);
+/* Zero-copy view for device consumers: the record.  GDP_ERR_STATE before the first refit. */
+int gdp_device_refit(const gdp_ransac* r, const gdp_refit_record** rec);
 
 /* ---- extension: homography warp of an input image on the device ---------------------------------
  * What the homography is for: one image resampled into the other's frame under the fitted model,

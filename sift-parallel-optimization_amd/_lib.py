@@ -171,6 +171,9 @@ SIGNATURES = {
     "gdp_device_inliers": (_c_int, [_p, _pp, _pp, _pp]),
     "gdp_ransac_layout": (_c_int, [_p, ctypes.POINTER(_c_size), ctypes.POINTER(_c_u32), ctypes.POINTER(_c_u32),
                                    ctypes.POINTER(_c_u32)]),
+    "gdp_refit_homography": (_c_int, [_p, _c_u32, ctypes.c_float, _p]),
+    "gdp_download_refit": (_c_int, [_p, _p]),
+    "gdp_device_refit": (_c_int, [_p, _pp]),
     "gdp_warp_create": (_c_int, [_pp, _p]),
     "gdp_warp_destroy": (None, [_p]),
     "gdp_warp_last_error": (ctypes.c_char_p, [_p]),

@@ -61,6 +61,7 @@ namespace {
 #include "gdp_pairs.inc"
 #include "gdp_match.inc"
 #include "gdp_ransac.inc"
+#include "gdp_refit.inc"
 #include "gdp_warp.inc"
 #include "gdp_guided.inc"
 #include "gdp_util.inc"
@@ -299,6 +300,7 @@ struct gdp_ransac : ErrorState {
     uint32_t* d_count = nullptr;           // one counter
     gdp_match_record* d_in = nullptr;      // the caller's list, allocated on first use
     uint32_t* d_in_count = nullptr;        // its length; kRaNoList = the match object's list
+    void* d_refit = nullptr;               // gdp_refit_homography's state (kRfBytes), allocated on the first refit
 };
 
 // gdp_warp_create: the warp's state.  It reads one gdp_ransac object (its model record) and, through
@@ -3698,6 +3700,7 @@ void gdp_ransac_destroy(gdp_ransac* r) {
     if (r->d_count) (void)hipFree(r->d_count);
     if (r->d_in) (void)hipFree(r->d_in);
     if (r->d_in_count) (void)hipFree(r->d_in_count);
+    if (r->d_refit) (void)hipFree(r->d_refit);
     delete r;
 }
 
@@ -3745,13 +3748,8 @@ int gdp_ransac_set_input(gdp_ransac* r, const gdp_match_record* host, size_t n) 
                          [](size_t, const gdp_match_record&) { return (int)GDP_OK; });
 } GDP_ABI_CATCH(r)
 
-int gdp_fit_homography(gdp_ransac* r, uint32_t hypotheses, uint32_t seed, float threshold, uint32_t min_inliers,
-                       void* stream) try {
-    if (!r) return GDP_ERR_ARG;
-    if (hypotheses == 0 || hypotheses > r->max_hypotheses)
-        return r->status(GDP_ERR_ARG, "gdp_fit_homography: %u hypotheses are not in 1..%u", hypotheses, r->max_hypotheses);
-    if (!(threshold >= 0.0f && std::isfinite(threshold)))  // a NaN fails the first
-        return r->status(GDP_ERR_ARG, "gdp_fit_homography: threshold %g is not finite and >= 0", (double)threshold);
+// The list a fit or a refit of r reads, as the launch resolves it
+static RaList ransac_list(const gdp_ransac* r) {
     const gdp_match* m = r->src;
     RaList list;
     list.src = reinterpret_cast<const uint4*>(m->d_out);
@@ -3759,6 +3757,17 @@ int gdp_fit_homography(gdp_ransac* r, uint32_t hypotheses, uint32_t seed, float 
     list.src_cap = (unsigned)std::min(m->cap[0], r->capacity);
     list.own = reinterpret_cast<const uint4*>(r->d_in);
     list.own_count = r->d_in_count;
+    return list;
+}
+
+int gdp_fit_homography(gdp_ransac* r, uint32_t hypotheses, uint32_t seed, float threshold, uint32_t min_inliers,
+                       void* stream) try {
+    if (!r) return GDP_ERR_ARG;
+    if (hypotheses == 0 || hypotheses > r->max_hypotheses)
+        return r->status(GDP_ERR_ARG, "gdp_fit_homography: %u hypotheses are not in 1..%u", hypotheses, r->max_hypotheses);
+    if (!(threshold >= 0.0f && std::isfinite(threshold)))  // a NaN fails the first
+        return r->status(GDP_ERR_ARG, "gdp_fit_homography: threshold %g is not finite and >= 0", (double)threshold);
+    const RaList list = ransac_list(r);
     GDP_HIP(r, hipSetDevice(r->device));
     hipStream_t st = ctx_of(r)->pick(stream);
     const float tt = threshold * threshold;  // one rounded float32 product
@@ -3813,6 +3822,74 @@ int gdp_device_inliers(const gdp_ransac* r, const gdp_match_record** records, co
     if (records) *records = r->d_out;
     if (count) *count = r->d_count;
     if (model) *model = r->d_model;
+    return GDP_OK;
+} GDP_ABI_CATCH(nullptr)
+
+// ---- extension: least-squares refit of the fitted homography (gdp_refit.inc) -----------------------
+// The state is still the gdp_ransac object's: the refit replaces its model record and inlier list in place.
+
+static_assert(sizeof(gdp_refit_record) == 96 && offsetof(gdp_refit_record, h) == 52 && 4 * kRfRecWords == sizeof(gdp_refit_record),
+              "six 16-byte stores, the layout gdp.h documents");
+
+static RfState refit_state(const gdp_ransac* r) {
+    RfState st;
+    st.rec = static_cast<uint32_t*>(r->d_refit);
+    st.flags = st.rec + kRfRecWords;
+    st.cand = st.flags + kRfFlagWords;
+    st.acc = reinterpret_cast<unsigned long long*>(st.cand + kRfCandWords);  // 208 bytes in: 8-byte aligned
+    return st;
+}
+
+int gdp_refit_homography(gdp_ransac* r, uint32_t rounds, float threshold, void* stream) try {
+    if (!r) return GDP_ERR_ARG;
+    if (rounds == 0 || rounds > kRfMaxRounds)
+        return r->status(GDP_ERR_ARG, "gdp_refit_homography: %u rounds are not in 1..%u", rounds, kRfMaxRounds);
+    if (!(threshold >= 0.0f && std::isfinite(threshold)))  // a NaN fails the first
+        return r->status(GDP_ERR_ARG, "gdp_refit_homography: threshold %g is not finite and >= 0", (double)threshold);
+    const RaList list = ransac_list(r);
+    GDP_HIP(r, hipSetDevice(r->device));
+    if (!r->d_refit) GDP_HIP(r, hipMalloc(&r->d_refit, kRfBytes));
+    hipStream_t st = ctx_of(r)->pick(stream);
+    const float tt = threshold * threshold;  // one rounded float32 product
+    const RfState s = refit_state(r);
+    RfList inl;
+    inl.recs = reinterpret_cast<const uint4*>(r->d_out);
+    inl.count = r->d_count;
+    inl.cap = (unsigned)r->capacity;
+    uint32_t* model = reinterpret_cast<uint32_t*>(r->d_model);
+    const unsigned sweep = (unsigned)std::min<size_t>(kRfMaxBlocks, std::max<size_t>(1, (r->capacity + kRfPerBlock - 1) / kRfPerBlock));
+    const unsigned each = (unsigned)((r->capacity + 255) / 256);
+    for (uint32_t round = 0; round < rounds; ++round) {
+        if (round == 0)
+            GDP_HIP(r, hipMemsetAsync(r->d_refit, 0, kRfBytes, st));
+        else
+            GDP_HIP(r, hipMemsetAsync(s.acc, 0, 8 * kRfAccWords, st));
+        hipLaunchKernelGGL(k_refit_origin, dim3(sweep), dim3(256), 0, st, inl, s, model);
+        hipLaunchKernelGGL(k_refit_moments<0>, dim3(sweep), dim3(256), 0, st, inl, s, model);
+        hipLaunchKernelGGL(k_refit_moments<1>, dim3(sweep), dim3(256), 0, st, inl, s, model);
+        hipLaunchKernelGGL(k_refit_solve, dim3(1), dim3(64), 0, st, inl, s, model);
+        hipLaunchKernelGGL(k_refit_count, dim3(sweep), dim3(256), 0, st, list, tt, s, model);
+        hipLaunchKernelGGL(k_refit_decide, dim3(1), dim3(64), 0, st, list, s, model, r->d_count, rounds, round);
+        hipLaunchKernelGGL(k_refit_inliers, dim3(each), dim3(256), 0, st, list, tt, s, model, reinterpret_cast<uint4*>(r->d_out),
+                           r->d_count);
+    }
+    GDP_HIP(r, hipGetLastError());
+    return GDP_OK;
+} GDP_ABI_CATCH(r)
+
+int gdp_download_refit(gdp_ransac* r, gdp_refit_record* rec) try {
+    if (!r || !rec) return r ? r->status(GDP_ERR_ARG, "gdp_download_refit: bad argument") : GDP_ERR_ARG;
+    if (!r->d_refit) {  // no refit yet
+        std::memset(rec, 0, sizeof *rec);
+        return GDP_OK;
+    }
+    return download_blocking(r, "gdp_download_refit", rec, r->d_refit, sizeof *rec);
+} GDP_ABI_CATCH(r)
+
+int gdp_device_refit(const gdp_ransac* r, const gdp_refit_record** rec) try {
+    if (!r || !rec) return GDP_ERR_ARG;
+    if (!r->d_refit) return GDP_ERR_STATE;
+    *rec = static_cast<const gdp_refit_record*>(r->d_refit);
     return GDP_OK;
 } GDP_ABI_CATCH(nullptr)
 

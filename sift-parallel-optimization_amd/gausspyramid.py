@@ -93,6 +93,12 @@ HOMOGRAPHY_DTYPE = np.dtype({"names": ["h", "hypothesis", "inliers", "matches", 
                              "formats": [(np.float32, (9,)), np.uint32, np.uint32, np.uint32, (np.uint32, (4,))],
                              "offsets": [0, 36, 40, 44, 48], "itemsize": 64})
 
+# struct gdp_refit_record (include/gdp.h): 96 bytes
+REFIT_DTYPE = np.dtype({"names": ["rounds", "accepted", "used", "skipped", "count_before", "count_after", "status", "kq", "kt",
+                                  "origin", "h", "reserved"],
+                        "formats": [np.uint32] * 9 + [(np.int32, (4,)), (np.float32, (9,)), (np.uint32, (2,))],
+                        "offsets": [0, 4, 8, 12, 16, 20, 24, 28, 32, 36, 52, 88], "itemsize": 96})
+
 
 # struct gdp_warp_record (include/gdp.h): 64 bytes
 WARP_DTYPE = np.dtype({"names": ["m", "model", "covered", "pixels", "sad", "direction", "reserved"],
@@ -886,6 +892,23 @@ class PyramidContext:
         check(lib().gdp_ransac_layout(r, ctypes.byref(cap), ctypes.byref(most), ctypes.byref(mt), ctypes.byref(ht)), r, "ransac")
         return cap.value, most.value, mt.value, ht.value
 
+    def refit_homography(self, rounds=1, threshold=3.0, stream=None):
+        """Refit the last fit's model over its inliers by least squares on the device
+        (gdp_refit_homography: exact 128-bit integer moments of the inlier coordinates quantised to
+        1/256 px, one 8 x 8 solve in float64; a round's candidate replaces the model record and the
+        inlier list in place when it accepts at least as many matches under `threshold`);
+        asynchronous on `stream`, no host read, so warp_image and guided_match after it consume the
+        refit model."""
+        r = self._handle("ransac")
+        check(lib().gdp_refit_homography(r, int(rounds), float(threshold), _stream_handle(stream)), r, "ransac")
+
+    def refit_record(self):
+        """The last refit's REFIT_DTYPE record (blocking; all 0 before any)."""
+        r = self._handle("ransac")
+        out = np.zeros(1, REFIT_DTYPE)
+        check(lib().gdp_download_refit(r, _ptr(out)), r, "ransac")
+        return out[0]
+
     # ------------------------------------------------------------------ guided matching (extension)
     # The gdp_guided object only reads the fit object and, through it, the match object's two sides.
     def set_guided_capacity(self, max_cells=0):
@@ -1172,6 +1195,13 @@ class GaussPyramid:
         self._ctx.set_ransac_input(matches)
         self._ctx.fit_homography(hypotheses, seed, threshold, min_inliers)
         return self._ctx.homography(), self._ctx.inliers()
+
+    def RefitHomography(self, rounds=1, threshold=3.0):
+        """Extension: refit the last FitHomography's model over its inliers by least squares on the
+        device (PyramidContext.refit_homography) and return (the model record, the inlier records
+        sorted by `query`, the REFIT_DTYPE record).  Nothing else is changed."""
+        self._ctx.refit_homography(rounds, threshold)
+        return self._ctx.homography(), self._ctx.inliers(), self._ctx.refit_record()
 
     def WarpImage(self, other=None, model=None, direction="train_to_query", fill=0):
         """Extension: resample `other`'s input image (the train side; None: the train side of the
